@@ -12,6 +12,13 @@ Launch: `python bench.py --gpus 1 --steps K --warmup W` or
 (any launcher that sets RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT will do: bench.py itself does not import
 torch.distributed -- the RCCL id travels over one TCP exchange, barrier and MAX over ranks through cg_allreduce_mean).
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the --steps sampling calls and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, the workload and the accept rate of the last call).  `--full` adds, after the timed steps, every report that takes runs of
+its own: the roofline against the fp64 peak measured on the GPU, the update path and the production shapes (--no-update-extras drops
+both), the CPU baseline (--no-cpu-baseline) and the energy check against the oracle (--no-energy-check).
+`--dump-outputs DIR` writes what the last timed call computed -- the walkers x (after the wrap into the box), their log-probabilities
+logp and the accept rate of that call -- as DIR/<name>.npy (float64; one file set per rank, `_rank<r>` appended when --gpus > 1).
 """
 import argparse, json, os, sys, time
 import numpy as np
@@ -323,6 +330,86 @@ def production_shapes(peak_tflops, mc_steps=50, stddev=0.1):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, suffix, x, logp, accept, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the last timed call's walkers, log-probabilities and accept rate as float64 .npy files.  Beyond `limit` bytes
+    the same fixed, seeded sample of walkers is taken from x and logp (their indices written as walker_index, float64)."""
+    os.makedirs(path, exist_ok=True)
+    B = x.shape[0]
+    per_walker = x[0].nbytes + logp[0].nbytes
+    keep = max(1, (limit - 4096) // (per_walker + 8))
+    arrays = {"accept_rate": np.array([accept], dtype=np.float64)}
+    if B * per_walker > limit - 4096:
+        idx = np.sort(np.random.default_rng(20261016).choice(B, keep, replace=False))
+        x, logp = x[idx], logp[idx]
+        arrays["walker_index"] = idx.astype(np.float64)
+    arrays.update(x=np.ascontiguousarray(x, dtype=np.float64), logp=np.ascontiguousarray(logp, dtype=np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
+
+
+def full_report(eng, args, world, n, dim, B, L, sp, theta, sidx, x_final, kernel_ms):
+    """--full: OUTSIDE the timed region, the reports that take runs of their own (roofline against the fp64 peak measured here, update
+    path, production shapes, CPU baseline, energy check); returns their keys of the JSON line and the names of those that failed."""
+    k_avg_s = kernel_ms / args.steps * 1e-3
+    fl = FLOPS_PER_WALKER_STEP.get(n)
+    by = BYTES_PER_WALKER_STEP.get(n)
+    eng.device_mode(False)
+    peak_fma = eng.microbench_fp64(0)
+    peak_mfma = eng.microbench_fp64(1)
+    peak = max(peak_fma, peak_mfma)
+    ach = (fl * B * args.mc_steps / k_avg_s / 1e12) if fl else None
+    traffic = None
+    tpath = os.path.join(ROOT, "profiles", "traffic_n%d_B%d.json" % (n, B))
+    if os.path.exists(tpath):               # HBM bytes per launch from the committed rocprofv3 --pmc passes
+        tj = json.load(open(tpath))
+        if tj.get("mc_steps") == args.mc_steps:
+            traffic = tj["bytes_per_launch"]
+    mfma_frac = None
+    if traffic is not None and tj.get("sq_insts_mfma_per_launch"):      # f64 MFMA share, from the committed SQ counter pass
+        mfma_frac = tj["sq_insts_mfma_per_launch"] * 2048.0 / k_avg_s / 1e12 / peak_mfma
+    roofline = {"bound": "mfma", "achieved": ach, "peak": peak, "unit": "TFLOP/s",
+                "frac": (ach / peak) if ach else None, "traffic": traffic,
+                "binds": "fp64 VALU / transcendental issue (compute label of the schema: the matrix cores carry only the dense layers, see mfma_frac; HBM: see hbm)",
+                "mfma_frac": mfma_frac,
+                "kernel": "k_mcmc", "kernel_avg_ms": k_avg_s * 1e3,
+                "note": "fp64 kernel: peak = measured v_fma_f64 / v_mfma_f64_16x16x4 rate on this GPU (%.1f / %.1f TFLOP/s); "
+                        "achieved = SURVEY 8(d) algorithmic %.3g flop/walker-step x %d walker-steps per launch / HIP-event kernel time"
+                        % (peak_fma, peak_mfma, fl or 0, B * args.mc_steps),
+                "hbm": {"achieved": (by * B * args.mc_steps / k_avg_s / 1e9) if by else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": (by * B * args.mc_steps / k_avg_s / 1e9 / HBM_PEAK_GBS) if by else None}}
+    cpu = None
+    energy = None
+    update = None
+    shapes = None
+    side_errors = []
+    if world == 1 and not args.no_update_extras:
+        try:                               # the metric line must survive a failing extra (reported, exit code 1 afterwards)
+            update = update_path_extras(eng, n, dim, L, sp, theta, sidx, x_final, peak, mc_steps=args.mc_steps)
+        except Exception as e:             # noqa: BLE001
+            update = {"error": repr(e)}; side_errors.append("update_path")
+    if world == 1 and not args.no_update_extras and n == 13:
+        try:
+            shapes = production_shapes(peak, mc_steps=args.mc_steps, stddev=args.mc_stddev)
+        except Exception as e:             # noqa: BLE001
+            shapes = {"error": repr(e)}; side_errors.append("shapes")
+    if world == 1 and not args.no_cpu_baseline:
+        try:
+            _, _, _, sidx0, x0 = synthetic(n, dim, B, args.Emax, 0)
+            cpu = cpu_baseline(n, dim, L, sp, theta, sidx0, x0, args.mc_steps, args.mc_stddev)
+        except Exception as e:             # noqa: BLE001 -- checker / baseline trouble (gcc, oracle build): keep the measured line
+            cpu = {"error": repr(e)}; side_errors.append("cpu_baseline")
+        if not args.no_energy_check:
+            try:
+                big = n > 16               # the torch oracle is minutes per walker beyond n = 13: fewer walkers there
+                energy = energy_check(eng, n, dim, L, sp, theta, sidx, x_final, n_split=4 if big else 64, n_exact=0 if big else 8)
+            except Exception as e:         # noqa: BLE001
+                energy = {"error": repr(e)}; side_errors.append("energy")
+    return {"roofline": roofline, "cpu_baseline": cpu, "energy": energy, "update_path": update, "shapes": shapes}, side_errors
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -337,6 +424,10 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-energy-check", action="store_true")
     ap.add_argument("--no-update-extras", action="store_true", help="skip the (untimed) SR-epoch / derivative-kernel report")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also the reports that take runs of their own: roofline "
+                    "(measured fp64 peak), update path, production shapes, CPU baseline, energy check")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed call's walkers, log-probabilities and accept rate "
+                    "as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -402,64 +493,15 @@ def main():
     lp = d_lp.download()
     ok = bool(np.isfinite(lp).all())
     x_final = d_x.download()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "_rank%d" % rank if world > 1 else "", x_final, lp, accept, limit=DUMP_LIMIT_BYTES // world)
 
     if rank == 0:
         walker_steps = float(B) * args.mc_steps * args.steps * world
         value = walker_steps / elapsed
-        k_avg_s = kernel_ms / args.steps * 1e-3
-        fl = FLOPS_PER_WALKER_STEP.get(n)
-        by = BYTES_PER_WALKER_STEP.get(n)
-        eng.device_mode(False)
-        peak_fma = eng.microbench_fp64(0)
-        peak_mfma = eng.microbench_fp64(1)
-        peak = max(peak_fma, peak_mfma)
-        ach = (fl * B * args.mc_steps / k_avg_s / 1e12) if fl else None
-        traffic = None
-        tpath = os.path.join(ROOT, "profiles", "traffic_n%d_B%d.json" % (n, B))
-        if os.path.exists(tpath):               # HBM bytes per launch from the committed rocprofv3 --pmc passes
-            tj = json.load(open(tpath))
-            if tj.get("mc_steps") == args.mc_steps:
-                traffic = tj["bytes_per_launch"]
-        mfma_frac = None
-        if traffic is not None and tj.get("sq_insts_mfma_per_launch"):      # f64 MFMA share, from the committed SQ counter pass
-            mfma_frac = tj["sq_insts_mfma_per_launch"] * 2048.0 / k_avg_s / 1e12 / peak_mfma
-        roofline = {"bound": "mfma", "achieved": ach, "peak": peak, "unit": "TFLOP/s",
-                    "frac": (ach / peak) if ach else None, "traffic": traffic,
-                    "binds": "fp64 VALU / transcendental issue (compute label of the schema: the matrix cores carry only the dense layers, see mfma_frac; HBM: see hbm)",
-                    "mfma_frac": mfma_frac,
-                    "kernel": "k_mcmc", "kernel_avg_ms": k_avg_s * 1e3,
-                    "note": "fp64 kernel: peak = measured v_fma_f64 / v_mfma_f64_16x16x4 rate on this GPU (%.1f / %.1f TFLOP/s); "
-                            "achieved = SURVEY 8(d) algorithmic %.3g flop/walker-step x %d walker-steps per launch / HIP-event kernel time"
-                            % (peak_fma, peak_mfma, fl or 0, B * args.mc_steps),
-                    "hbm": {"achieved": (by * B * args.mc_steps / k_avg_s / 1e9) if by else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                            "frac": (by * B * args.mc_steps / k_avg_s / 1e9 / HBM_PEAK_GBS) if by else None}}
-        cpu = None
-        energy = None
-        update = None
-        shapes = None
-        side_errors = []
-        if world == 1 and not args.no_update_extras:
-            try:                               # the metric line must survive a failing extra (reported, exit code 1 afterwards)
-                update = update_path_extras(eng, n, dim, L, sp, theta, sidx, x_final, peak, mc_steps=args.mc_steps)
-            except Exception as e:             # noqa: BLE001
-                update = {"error": repr(e)}; side_errors.append("update_path")
-        if world == 1 and not args.no_update_extras and n == 13:
-            try:
-                shapes = production_shapes(peak, mc_steps=args.mc_steps, stddev=args.mc_stddev)
-            except Exception as e:             # noqa: BLE001
-                shapes = {"error": repr(e)}; side_errors.append("shapes")
-        if world == 1 and not args.no_cpu_baseline:
-            try:
-                _, _, _, sidx0, x0 = synthetic(n, dim, B, args.Emax, 0)
-                cpu = cpu_baseline(n, dim, L, sp, theta, sidx0, x0, args.mc_steps, args.mc_stddev)
-            except Exception as e:             # noqa: BLE001 -- checker / baseline trouble (gcc, oracle build): keep the measured line
-                cpu = {"error": repr(e)}; side_errors.append("cpu_baseline")
-            if not args.no_energy_check:
-                try:
-                    big = n > 16               # the torch oracle is minutes per walker beyond n = 13: fewer walkers there
-                    energy = energy_check(eng, n, dim, L, sp, theta, sidx, x_final, n_split=4 if big else 64, n_exact=0 if big else 8)
-                except Exception as e:         # noqa: BLE001
-                    energy = {"error": repr(e)}; side_errors.append("energy")
+        extras, side_errors = {}, []
+        if args.full:
+            extras, side_errors = full_report(eng, args, world, n, dim, B, L, sp, theta, sidx, x_final, kernel_ms)
         out = {"metric": "walker-steps/sec (batch x mcsteps/s), n=%d 2D batch %d" % (n, B), "value": value,
                "unit": "walker-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -468,8 +510,8 @@ def main():
                                       "(MCMC chain incl. flow+Jacobian+Slater logp), in-kernel Philox RNG" % (n, args.Emax, B, args.mc_steps, args.mc_stddev),
                           "walkers_per_gpu": B, "mc_steps": args.mc_steps, "threads_per_walker": eng.launch_info()["threads"],
                           "lds_bytes_per_walker": eng.launch_info()["lds_bytes"]},
-               "accept_rate": accept, "finite": ok, "comm": comm_kind, "roofline": roofline, "cpu_baseline": cpu,
-               "energy": energy, "update_path": update, "shapes": shapes}
+               "accept_rate": accept, "finite": ok, "comm": comm_kind, "full": bool(args.full)}
+        out.update(extras)
         print(json.dumps(out), flush=True)
         if side_errors:
             print("bench.py: %s failed (see the JSON line)" % ", ".join(side_errors), file=sys.stderr)

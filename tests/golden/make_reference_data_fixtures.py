@@ -11,6 +11,8 @@ runs on the GPU box):
   shipped_n29_rs10.npz / shipped_n29_rs1.npz / shipped_n57_rs10.npz
                                      a slice of the shipped walkers (`x` of epoch_*.pkl), the trained
                                      flow parameters and the matching published data.txt row.
+  shipped_n29_rs10_epoch_003000_dev2.pkl   (--checkpoint) the shipped checkpoint file itself, byte for byte,
+                                     with `x` cut to its first 2 device rows (512 walkers)
 
 Orbital ordering: `sp_orbitals` sorts degenerate integer energies with
 numpy's *unstable* default argsort (src/orbitals.py:42).  The shipped models only reproduce
@@ -19,7 +21,7 @@ their published free energies with the legacy (non-SIMD) quicksort tie order fol
 src/orbitals.py:53 runs JAX's stable argsort).  The legacy order is obtained by importing the
 reference's own src/orbitals.py in a child process with numpy's SIMD sort kernels disabled.
 """
-import os, sys, subprocess, pickle, glob, json
+import io, os, sys, subprocess, pickle, pickletools, glob, json
 import numpy as np
 
 REF = "/root/reference"
@@ -84,6 +86,30 @@ def shipped(n, rs, epoch, nwalk, out):
     print(out, x[:nwalk].shape, theta.shape, row)
 
 
+def trimmed_checkpoint(n, rs, epoch, ndev, out):
+    """The shipped checkpoint file in the reference's own pickle stream, cut to the first `ndev` rows of the leading (device) axis
+    of `x`: only the shape's leading entry, the length of the walkers' BINBYTES and the bytes after the cut change."""
+    d = glob.glob("%s/data/n_%d_dim_2_rs_%s_*" % (REF, n, rs))[0]
+    src = os.path.join(d, "epoch_%06d.pkl" % epoch)
+    raw = open(src, "rb").read()
+    ops = list(pickletools.genops(raw))
+    i = next(k for k, (op, arg, _) in enumerate(ops) if op.name == "SHORT_BINUNICODE" and arg == "x")
+    k = next(k for k in range(i, len(ops)) if ops[k][0].name == "MARK" and ops[k + 5][0].name == "TUPLE"
+             and ops[k + 3][1] == n and ops[k + 4][1] == 2)                  # the shape tuple (ndevices, batch / ndevices, n, 2)
+    op, lead, p = ops[k + 1]
+    assert op.name == "BININT1" and 0 < ndev <= lead
+    q = next(pos for op, _, pos in ops[k:] if op.name == "BINBYTES")            # the walkers' raw float64 data
+    size = int.from_bytes(raw[q + 1:q + 5], "little")
+    keep = size // lead * ndev
+    cut = raw[:p + 1] + bytes([ndev]) + raw[p + 2:q + 1] + keep.to_bytes(4, "little") + raw[q + 5:q + 5 + keep] + raw[q + 5 + size:]
+    a = _Unpickler(open(src, "rb")).load()
+    b = _Unpickler(io.BytesIO(cut)).load()
+    assert np.array_equal(np.asarray(b["x"]), np.asarray(a["x"])[:ndev]) and set(a) == set(b)
+    with open(os.path.join(HERE, out), "wb") as f:
+        f.write(cut)
+    print(out, np.asarray(b["x"]).shape, len(cut) // 1024, "KB")
+
+
 def shipped_run(n, rs, nwalk):
     """One production run of data/n_*: a slice of the final walkers, the trained flow and Transformer parameters and the last
     published data.txt row, in ONE npz under tests/golden/shipped_runs/ (all 18 runs: round-3 widening of the reference-held pin)."""
@@ -122,6 +148,9 @@ def van_fixture(src_pkl, key, out, extra):
 
 
 if __name__ == "__main__":
+    if "--checkpoint" in sys.argv:             # the real checkpoint file tests/test_host_logic.py::test_checkpoint_interop loads
+        trimmed_checkpoint(29, "10.0", 3000, 2, "shipped_n29_rs10_epoch_003000_dev2.pkl")
+        sys.exit(0)
     if "--runs" in sys.argv:                   # round 3: all 18 production runs + the two larger pretrained models
         for n, nw in ((29, 192), (49, 128), (57, 128)):
             for rs in ("0.25", "0.5", "1.0", "3.0", "5.0", "10.0"):

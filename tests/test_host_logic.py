@@ -354,14 +354,16 @@ def test_checkpoint_interop(tmp_path):
         f.write("     1  -4.870600  0.002007  -4.870600  0.002007  0.619739  0.000123  -5.490339  0.002010  0.000000  0.000000  0.5369\n")
     lg = ck.load_log(os.path.join(str(tmp_path), "data.txt"))
     assert lg["E"][0] == -4.8706 and lg["accept_rate"][0] == 0.5369
-    # container-only cross-check against a shipped checkpoint and its committed fixture slice
-    import glob
-    d = glob.glob("/root/reference/data/n_29_dim_2_rs_10.0_*")
-    if d:
-        c = cg.load_data(cg.ckpt_filename(3000, d[0]))
-        fix = np.load(GOLDEN + "/shipped_n29_rs10.npz")
-        th = np.concatenate([np.asarray(c["params_flow"][k][l]).ravel() for k in sorted(c["params_flow"]) for l in ("b", "w")])
-        assert np.array_equal(th, fix["theta"]) and np.array_equal(c["x"].reshape(-1, 29, 2)[:512], fix["x"])
+    # cross-check against a shipped checkpoint (the file itself, its walkers cut to 2 device rows: tests/golden/
+    # make_reference_data_fixtures.py --checkpoint) and its committed fixture slice
+    import shutil
+    shipped = os.path.join(str(tmp_path), "shipped")
+    os.makedirs(shipped)
+    shutil.copyfile(GOLDEN + "/shipped_n29_rs10_epoch_003000_dev2.pkl", cg.ckpt_filename(3000, shipped))
+    c = cg.load_data(cg.ckpt_filename(3000, shipped))
+    fix = np.load(GOLDEN + "/shipped_n29_rs10.npz")
+    th = np.concatenate([np.asarray(c["params_flow"][k][l]).ravel() for k in sorted(c["params_flow"]) for l in ("b", "w")])
+    assert np.array_equal(th, fix["theta"]) and np.array_equal(c["x"].reshape(-1, 29, 2)[:512], fix["x"])
 
 
 def _load_van(name):

@@ -13,13 +13,13 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 if [ "$STAGE" != "2" ]; then
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 echo "bench done: $(cut -c1-160 $OUT/bench.json)"
-rocprofv3 --kernel-trace --stats -d $OUT/st_bench -- python3 bench.py --no-cpu-baseline --no-energy-check --no-update-extras > $OUT/bench_under_rocprof.json 2> $OUT/st_bench.log
+rocprofv3 --kernel-trace --stats -d $OUT/st_bench -- python3 bench.py --full --no-cpu-baseline --no-energy-check --no-update-extras > $OUT/bench_under_rocprof.json 2> $OUT/st_bench.log
 python3 tools/profile_summary.py stats $OUT/st_bench > $OUT/kernel_stats_bench_n13_B8192.csv
 for pmc in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_VMEM SQ_INSTS_LDS SQ_INSTS_MFMA SQ_BUSY_CYCLES"; do
   nm=$(echo $pmc | cut -d' ' -f1 | tr 'A-Z' 'a-z')
-  rocprofv3 --pmc $pmc -d $OUT/pmc_bench_$nm -- python3 bench.py --no-cpu-baseline --no-energy-check --no-update-extras --steps 3 --warmup 1 > $OUT/pmc_bench_$nm.log 2>&1
+  rocprofv3 --pmc $pmc -d $OUT/pmc_bench_$nm -- python3 bench.py --full --no-cpu-baseline --no-energy-check --no-update-extras --steps 3 --warmup 1 > $OUT/pmc_bench_$nm.log 2>&1
   python3 tools/profile_summary.py pmc $OUT/pmc_bench_$nm k_mcmc > $OUT/pmc_${nm}_k_mcmc_n13_B8192.txt
 done
 echo "bench counters done"
@@ -43,11 +43,11 @@ rocprofv3 --kernel-trace --stats -d $OUT/st_solve -- python3 tools/solve_timing.
 python3 tools/profile_summary.py stats $OUT/st_solve > $OUT/kernel_stats_spd_solve_P5907.csv
 python3 tools/profile_summary.py timeline $OUT/st_solve chol 40 > $OUT/timeline_spd_solve_P5907.txt
 echo "solve done"
-python3 bench.py --n 29 --batch 2048 --Emax 25 --no-update-extras > $OUT/bench_n29.json 2> $OUT/bench_n29.err
-python3 bench.py --n 57 --batch 512 --Emax 49 --no-update-extras > $OUT/bench_n57.json 2> $OUT/bench_n57.err
-rocprofv3 --kernel-trace --stats -d $OUT/st_n29 -- python3 bench.py --n 29 --batch 2048 --Emax 25 --no-cpu-baseline --no-energy-check --no-update-extras > /dev/null 2> $OUT/st_n29.log
+python3 bench.py --full --n 29 --batch 2048 --Emax 25 --no-update-extras > $OUT/bench_n29.json 2> $OUT/bench_n29.err
+python3 bench.py --full --n 57 --batch 512 --Emax 49 --no-update-extras > $OUT/bench_n57.json 2> $OUT/bench_n57.err
+rocprofv3 --kernel-trace --stats -d $OUT/st_n29 -- python3 bench.py --full --n 29 --batch 2048 --Emax 25 --no-cpu-baseline --no-energy-check --no-update-extras > /dev/null 2> $OUT/st_n29.log
 python3 tools/profile_summary.py stats $OUT/st_n29 > $OUT/kernel_stats_bench_n29_B2048.csv
-rocprofv3 --kernel-trace --stats -d $OUT/st_n57 -- python3 bench.py --n 57 --batch 512 --Emax 49 --no-cpu-baseline --no-energy-check --no-update-extras > /dev/null 2> $OUT/st_n57.log
+rocprofv3 --kernel-trace --stats -d $OUT/st_n57 -- python3 bench.py --full --n 57 --batch 512 --Emax 49 --no-cpu-baseline --no-energy-check --no-update-extras > /dev/null 2> $OUT/st_n57.log
 python3 tools/profile_summary.py stats $OUT/st_n57 > $OUT/kernel_stats_bench_n57_B512.csv
 if [ -f coulombgas_amd/lib/diag/libcg_stamps.so ]; then
   for cfg in "13 8192" "29 2048" "57 512"; do set -- $cfg
