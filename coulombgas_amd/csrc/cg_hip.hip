@@ -276,9 +276,7 @@ int cg_create(cg_ctx** out, int device, int n, int dim, int depth, int spsize, i
     c->P = c->gm.nparam;
     memset(&c->lay, 0, sizeof(c->lay));
     if (fast_ok) {
-#define CG_X(D, HS, HT) if (dim == D && spsize == HS && tpsize == HT) c->P = CgFast<D, HS, HT>::NPARAM;
-        CG_FAST_CONFIGS(CG_X)
-#undef CG_X
+        cg_with_config<CgFastConfigs>(dim, spsize, tpsize, [&](auto cfg) { return c->P = CgFast<cfg.D, cfg.HS, cfg.HT>::NPARAM; });
         c->lay = cg_fast_layout(n, dim, spsize, tpsize, true, spsize == 16 && tpsize == 16);
         // maximum size of the LDS-resident path: J (n d)^2 + the per-particle factors must fit 160 KiB.  Beyond it (n > ~64
         // at d = 2) the same model runs on the general path (HBM workspace), which provides every entry point.
@@ -567,7 +565,7 @@ static int van_launch(cg_ctx* c, bool sample, int B, int* sidx_dev, const double
     int rc;
     // compile-time dimensions pay when a CU holds few waves (latency-bound: n = 57, B = 512: 1.29 -> 1.05 ms; n = 29, B = 2048: 1.22 -> 1.02);
     // with every SIMD full (n = 13, B = 8192) the unrolled products cost more registers than they hide: 1.27 against 1.72 ms
-    const bool shipped = m.ms == 16 && m.hs == 32 && m.nl == 2 && m.nh == 4 && cg_env_int("CG_VAN_STATIC", B <= 16 * c->cu_count ? 1 : 0);
+    const bool shipped = m.ms == 16 && m.hs == 32 && m.nl == 2 && m.nh == 4 && cg_tune::van_static(B, c->cu_count);
 #define CG_VAN_LAUNCH(S, H)                                                                                                              \
     { if ((rc = set_lds(c, k_van<S, H>, lds))) return rc;                                                                                \
       hipLaunchKernelGGL((k_van<S, H>), dim3(grid), dim3(64 * waves), lds, c->stream, m, (const double*)c->d_van, (const double*)c->d_van_sp, B, \
@@ -636,7 +634,8 @@ int cg_van_scores_compute(cg_ctx* c, const int32_t* state_idx, int B) {
     int waves = 0, plds = 1;
     // (workgroups of <= 4 waves of the shipped architecture run the register-accumulating kernel, which is pinned to one wave per SIMD:
     // never more than 4 waves per CU whatever the LDS would allow -- the estimates below count that)
-    const bool reg_possible = cg_env_int("CG_VAN_GRAD_REG", 1) > 0 && m.ms == 16 && m.hs == 32 && m.nl == 2 && m.nh == 4 && m.dim * m.ms <= 64 && m.M <= 256;
+    const int regmode = cg_tune::van_grad_reg();
+    const bool reg_possible = regmode > 0 && m.ms == 16 && m.hs == 32 && m.nl == 2 && m.nh == 4 && m.dim * m.ms <= 64 && m.M <= 256;
     auto cap = [&](int w, int per_cu) { return (reg_possible && w <= 4) ? std::min(per_cu, 4) : per_cu; };
     { int best = 0;
       for (int w = 1; w <= 8; ++w) {
@@ -657,13 +656,12 @@ int cg_van_scores_compute(cg_ctx* c, const int32_t* state_idx, int B) {
         const int rounds1 = (B + c->cu_count * per_cu1 - 1) / (c->cu_count * per_cu1), rounds0 = (B + c->cu_count * best0 - 1) / (c->cu_count * best0);
         if (rounds0 * 7 <= rounds1 * 5) { plds = 0; waves = wsel; }
     }
-    if (cg_env_int("CG_VAN_GRAD_REG", 1) == 2 && waves > 4) waves = 4;
+    if (regmode == 2 && waves > 4) waves = 4;
     const size_t lds = (plds ? pbytes : 0) + waves * wbytes;
     if (lds > 160 * 1024) CG_FAIL(c, CG_ERR_UNSUPPORTED, "cg_van_scores_compute: one sample needs %zu bytes of LDS", wbytes);
     const int grid = std::min((B + waves - 1) / waves, c->cu_count * 4);
     const size_t stash_per_wave = (size_t)(m.n > 1 ? m.n - 1 : 1) * cg_van_token_stash(m);
     if ((rc = ensure_ws(c, sizeof(double) * stash_per_wave * (size_t)grid * waves))) return rc;
-    const int regmode = cg_env_int("CG_VAN_GRAD_REG", 1);
     const bool shipped = m.ms == 16 && m.hs == 32 && m.nl == 2 && m.nh == 4;
     const bool reg_ok = regmode > 0 && waves <= 4 && shipped && m.dim * m.ms <= 64 && m.M <= 256;
 #define CG_VAN_REG_LAUNCH(MR)                                                                                                         \

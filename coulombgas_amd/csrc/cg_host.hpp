@@ -1,6 +1,5 @@
-// cg_host.hpp -- host-side state shared by the translation units of libcoulombgas_hip.so (cg_hip.hip: context, Ewald,
-// solver, communicator; cg_k_sampler.hip: log Psi / Metropolis kernels; cg_k_derivs.hip: grad / Laplacian, theta-VJP,
-// scores; cg_k_generic.hip: general-depth kernels).  The library is split so that the units compile in parallel.
+// cg_host.hpp -- host-side state and launch helpers shared by the translation units of libcoulombgas_hip.so (build.py: HIP_UNITS; the
+// library is split so that the units compile in parallel).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>
@@ -186,11 +185,51 @@ static CgDev make_dev(const cg_ctx* c) {
     return m;
 }
 
-// launch-shape overrides for tuning runs (unset: the built-in choice)
+// Tuning table: every CG_* environment variable the library reads -- name, built-in choice, meaning -- and the only place that reads
+// one (INTEGRATION.md section 5 lists the same names).  Each is read at every call that uses it (tests and the sweeps under tools/ change
+// them between calls on a live context); CG_CHOL_QUADRANT_BLOCKS alone is kept in a function-local static by its user (cg_solve.inc).
+// Not here: CG_PLAN_DEBUG (prints the placement plan), read with getenv in cg_big.hpp, which the host-side tools compile without HIP.
 static inline int cg_env_int(const char* name, int dflt) {
     const char* v = getenv(name);
     return v && *v ? atoi(v) : dflt;
 }
+namespace cg_tune {
+// planned kernels of the larger systems (cg_k_big.hip: n > 16, (dim 2, 16, 16) flow)
+inline int big()                     { return cg_env_int("CG_BIG", 1); }                             // 0: the first-generation kernels instead
+inline int big_lap()                 { return cg_env_int("CG_BIG_LAP", 1); }                         // 0: ... for grad / Laplacian only
+inline int big_fused()               { return cg_env_int("CG_BIG_FUSED", 1); }                       // 0: cg_grad_laplacian_scores runs the two kernels one after the other
+inline int big_nt(int n, int D)      { return cg_env_int("CG_BIG_NT", n * D <= 64 ? 256 : 512); }    // threads per workgroup (256 / 512)
+inline int big_per_cu()              { return cg_env_int("CG_BIG_PER_CU", 2); }                      // workgroups per CU (read for 256 threads; 512: always 1)
+inline int big_lds_kb(int per_cu)    { return cg_env_int("CG_BIG_LDS_KB", per_cu == 2 ? 79 : 159); } // LDS the plan may use
+inline int big_rounds()              { return cg_env_int("CG_BIG_ROUNDS", 4); }                      // rounds of workgroups per launch of a chunked batch
+inline int big_debug()               { return cg_env_int("CG_BIG_DEBUG", 0); }                       // 1: print the layout to stderr at every call
+// first-generation derivative kernels where a system does not fit LDS (cg_k_derivs.inc); fit: workgroups whose LDS fits a CU
+inline int lap_nt(int n, int D)      { return cg_env_int("CG_LAP_NT", n * D <= 64 ? 256 : 512); }    // k_grad_lap2: threads per workgroup (256 / 512)
+inline int lap_lds_kb()              { return cg_env_int("CG_LAP_LDS_KB", 156); }                         // its LDS budget
+inline int lap_per_cu(int fit)       { return cg_env_int("CG_LAP_PER_CU", std::min(fit, 2)); }       // workgroups per CU of a launch
+inline int vjp_nt()                  { return cg_env_int("CG_VJP_NT", 512); }                        // k_param_vjp: the same three
+inline int vjp_lds_kb()              { return cg_env_int("CG_VJP_LDS_KB", 156); }
+inline int vjp_per_cu(int fit)       { return cg_env_int("CG_VJP_PER_CU", std::min(fit, 2)); }
+inline int vjp_occ(int n, int D)     { return cg_env_int("CG_VJP_OCC", n * D > 64 ? 1 : 0); }        // 1: the 128-register instantiation, two 512-thread workgroups per CU
+// fused grad / Laplacian + scores at n <= 16 (cg_k_derivs_a.hip)
+inline int small_fused()             { return cg_env_int("CG_SMALL_FUSED", 1); }                     // 0: the two calls one after the other
+inline int small_fused_chunk()       { return cg_env_int("CG_SMALL_FUSED_CHUNK", 16384); }           // walkers per launch (77 KB of stash each: 1.2 GB at most)
+// Transformer density matrix (cg_k_van.hip, cg_hip.hip)
+// CG_VAN_PAR, positions in parallel (0 / 1), has two built-in choices: the several-samples-per-wave kernel of short sequences is on at every
+// size it serves, the one-sample-per-wave kernel only from n = 20 (below it most lanes have no position and the sequential kernel wins)
+inline int van_par(bool packed, int n) { return cg_env_int("CG_VAN_PAR", packed || n >= 20 ? 1 : 0); }
+inline int van_packed()              { return cg_env_int("CG_VAN_PACKED", 1); }                      // 0: never several samples per wave
+inline int van_packed_maxn()         { return cg_env_int("CG_VAN_PACKED_MAXN", 33); }                // ... up to this many particles
+inline int van_par_waves()           { return cg_env_int("CG_VAN_PAR_WAVES", 0); }                   // waves per workgroup of both (0: as many as LDS allows, <= 4)
+inline int van_grad_reg()            { return cg_env_int("CG_VAN_GRAD_REG", 1); }                    // sequential score kernel: -1 runtime dimensions, 0 compile-time
+                                       // dimensions, 1 (> 0) + the gradient row in registers where the workgroup has <= 4 waves, 2 also holds it to <= 4 waves
+inline int van_static(int B, int cu) { return cg_env_int("CG_VAN_STATIC", B <= 16 * cu ? 1 : 0); }   // sampler / log-probability with compile-time model dimensions
+// solver (cg_solve.inc)
+inline int fisher_slices()           { return cg_env_int("CG_FISHER_SLICES", 0); }                   // batch slices of cg_fisher_real (0: by occupancy)
+inline int chol_quadrant_blocks()    { return cg_env_int("CG_CHOL_QUADRANT_BLOCKS", 1024); }         // fewer 64 x 64 blocks than this: a wave per quadrant (once per process)
+inline int chol_no_lookahead()       { return cg_env_int("CG_CHOL_NO_LOOKAHEAD", 0); }               // 1: the whole trailing update on the context's stream
+inline int chol_block_nt()           { return cg_env_int("CG_CHOL_BLOCK_NT", 1024); }                // threads of the diagonal-block kernel (256 / 512 / 1024)
+}  // namespace cg_tune
 
 template <class K>
 static int set_lds(cg_ctx* c, K kernel, size_t bytes) {
@@ -214,6 +253,16 @@ static int ensure_ws(cg_ctx* c, size_t bytes) {
     CG_HIP(c, hipMalloc(&c->ws, bytes));
     c->ws_cap = bytes;
     return CG_OK;
+}
+
+// A batch of B walkers, one per workgroup, in launches of `chunk`: the workspace holds a slot of per_wg doubles for each workgroup of a launch
+// (+ the pad doubles that caller has always allocated after the last one); launch(grid, w0) issues the kernel for the walkers [w0, w0 + grid).  Returns 1 (launched) or an error.
+template <class K, class L>
+static int cg_launch_chunked(cg_ctx* c, K kernel, size_t lds, size_t per_wg, size_t pad, int chunk, int B, L&& launch) {
+    if (int rc = ensure_ws(c, sizeof(double) * (per_wg * chunk + pad))) return rc;
+    if (int rc = set_lds(c, kernel, lds)) return rc;
+    for (int w0 = 0; w0 < B; w0 += chunk) launch(std::min(chunk, B - w0), w0);
+    return 1;
 }
 
 // general-depth launches (cg_k_generic.hip); every array argument is a device pointer

@@ -37,36 +37,38 @@ __global__ void __launch_bounds__(NT, NT <= 256 ? 2 : 1) k_scores_big(CgDev m, c
 #endif
 }
 
+// The launch shape of the three entry points below, from the system size, the chip and the CG_BIG_* variables: one function, so that the
+// fused call plans and chunks exactly as the two separate calls do (its results are theirs bit for bit).
+struct CgBigShape { int nt, per_cu; size_t cap; int chunk; };   // threads per workgroup, workgroups per CU, doubles of LDS for the plan, walkers per launch
+static CgBigShape big_shape(const cg_ctx* c, int D, int B) {
+    CgBigShape s;
+    s.nt = cg_tune::big_nt(c->n, D);
+    s.per_cu = s.nt == 256 ? cg_tune::big_per_cu() : 1;
+    s.cap = (size_t)cg_tune::big_lds_kb(s.per_cu) * 1024 / sizeof(double) - CG_TAB_DOUBLES;
+    s.chunk = std::min(B, c->cu_count * s.per_cu * cg_tune::big_rounds());
+    return s;
+}
+
 // scores of B walkers by the planned kernel of the larger systems: 1 launched, 0 not served, < 0 error
 int cg_big_scores(cg_ctx* c, const CgDev& m, const double* x, const int* sidx, int B, double* score) {
     constexpr int D = 2, HS = 16, HT = 16;
     if (c->dim != D || c->hs != HS || c->ht != HT || c->n <= 16) return 0;      // (n <= 16: k_scores, everything in LDS)
-    {
-        int rc;
-        const int n = c->n;
-        if (cg_env_int("CG_BIG", 1) == 0) return 0;
-        const int bnt = cg_env_int("CG_BIG_NT", n * D <= 64 ? 256 : 512);
-        const int per_cu = bnt == 256 ? cg_env_int("CG_BIG_PER_CU", 2) : 1;
-        const size_t capb = (size_t)cg_env_int("CG_BIG_LDS_KB", per_cu == 2 ? 79 : 159) * 1024;
-        const auto bl = CgBig<D, HS, HT>::layout_scores(n, bnt, capb / sizeof(double) - CG_TAB_DOUBLES);
-        if (cg_env_int("CG_BIG_DEBUG", 0))
-            fprintf(stderr, "cg_big_scores n=%d nt=%d ok=%d lds %u doubles, ws %u doubles per workgroup; J %d JT %d Dm %d Dinv %d s1k %d s2k %d m1k %d Bb %d Vb %d Ub %d Rb %d u1b %d u1i %d sg1b %d\n",
-                    n, bnt, bl.ok, bl.lds_total, bl.ws_total, bl.c.J, bl.c.JT, bl.c.Dm, bl.c.Dinv, bl.s1k, bl.s2k, bl.m1k, bl.Bb, bl.Vb, bl.Ub, bl.Rb, bl.u1b, bl.u1i, bl.sg1b);
-        if (!bl.ok) return 0;
-        const size_t lds = sizeof(double) * (CG_TAB_DOUBLES + (size_t)bl.lds_total);
-        const int chunk = std::min(B, c->cu_count * per_cu * cg_env_int("CG_BIG_ROUNDS", 4));
-        if ((rc = ensure_ws(c, sizeof(double) * ((size_t)bl.ws_total * chunk + 8)))) return rc;
-        auto go = [&](auto ntc) -> int {
-            constexpr int NT = decltype(ntc)::value;
-            if (int r = set_lds(c, k_scores_big<D, HS, HT, NT>, lds)) return r;
-            for (int w0 = 0; w0 < B; w0 += chunk)
-                hipLaunchKernelGGL((k_scores_big<D, HS, HT, NT>), dim3(std::min(chunk, B - w0)), dim3(NT), lds, c->stream, m, (const double*)c->d_theta,
-                                   (const double*)c->d_spk, (const double*)c->d_tab, x, sidx, B, w0, score, (double*)c->ws, bl);
-            return 0;
-        };
-        if ((rc = bnt == 256 ? go(std::integral_constant<int, 256>{}) : go(std::integral_constant<int, 512>{}))) return rc;
-        return 1;
-    }
+    if (cg_tune::big() == 0) return 0;
+    const int n = c->n;
+    const CgBigShape sh = big_shape(c, D, B);
+    const auto bl = CgBig<D, HS, HT>::layout_scores(n, sh.nt, sh.cap);
+    if (cg_tune::big_debug())
+        fprintf(stderr, "cg_big_scores n=%d nt=%d ok=%d lds %u doubles, ws %u doubles per workgroup; J %d JT %d Dm %d Dinv %d s1k %d s2k %d m1k %d Bb %d Vb %d Ub %d Rb %d u1b %d u1i %d sg1b %d\n",
+                n, sh.nt, bl.ok, bl.lds_total, bl.ws_total, bl.c.J, bl.c.JT, bl.c.Dm, bl.c.Dinv, bl.s1k, bl.s2k, bl.m1k, bl.Bb, bl.Vb, bl.Ub, bl.Rb, bl.u1b, bl.u1i, bl.sg1b);
+    if (!bl.ok) return 0;
+    const size_t lds = sizeof(double) * (CG_TAB_DOUBLES + (size_t)bl.lds_total);
+    return cg_with_nt_equal<256, 512>(sh.nt, [&](auto ntc) -> int {
+        constexpr int NT = ntc;
+        return cg_launch_chunked(c, k_scores_big<D, HS, HT, NT>, lds, bl.ws_total, 8, sh.chunk, B, [&](int grid, int w0) {
+            hipLaunchKernelGGL((k_scores_big<D, HS, HT, NT>), dim3(grid), dim3(NT), lds, c->stream, m, (const double*)c->d_theta,
+                               (const double*)c->d_spk, (const double*)c->d_tab, x, sidx, B, w0, score, (double*)c->ws, bl);
+        });
+    });
 }
 
 template <int D, int HS, int HT, int NT>
@@ -90,30 +92,22 @@ __global__ void __launch_bounds__(NT, NT <= 256 ? 2 : 1) k_gradlap_big(CgDev m, 
 int cg_big_grad_lap(cg_ctx* c, const CgDev& m, const double* x, const int* sidx, int B, int mode, const double* v, double* grad, double* lap) {
     constexpr int D = 2, HS = 16, HT = 16;
     if (c->dim != D || c->hs != HS || c->ht != HT || (mode != 1 && mode != 2) || !v || c->n <= 16) return 0;   // (n <= 16: k_grad_lap2 in every mode)
-    int rc;
+    if (cg_tune::big() == 0 || cg_tune::big_lap() == 0) return 0;
     const int n = c->n;
-    if (cg_env_int("CG_BIG", 1) == 0 || cg_env_int("CG_BIG_LAP", 1) == 0) return 0;
-    const int bnt = cg_env_int("CG_BIG_NT", n * D <= 64 ? 256 : 512);
-    const int per_cu = bnt == 256 ? cg_env_int("CG_BIG_PER_CU", 2) : 1;
-    const size_t capb = (size_t)cg_env_int("CG_BIG_LDS_KB", per_cu == 2 ? 79 : 159) * 1024;
-    const auto bl = CgBig<D, HS, HT>::layout_gradlap(n, bnt, mode, capb / sizeof(double) - CG_TAB_DOUBLES);
-    if (cg_env_int("CG_BIG_DEBUG", 0))
+    const CgBigShape sh = big_shape(c, D, B);
+    const auto bl = CgBig<D, HS, HT>::layout_gradlap(n, sh.nt, mode, sh.cap);
+    if (cg_tune::big_debug())
         fprintf(stderr, "cg_big_grad_lap n=%d nt=%d mode=%d ok=%d lds %u doubles, ws %u doubles per workgroup; J %d JT %d Dm %d Dinv %d Ta %d Am %d Hk %d Bb %d Vb %d Ub %d Rb %d jp %d Vt %d Bmt %d Upt %d Jp %d\n",
-                n, bnt, mode, bl.ok, bl.lds_total, bl.ws_total, bl.c.J, bl.c.JT, bl.c.Dm, bl.c.Dinv, bl.Ta, bl.Am, bl.Hk, bl.Bb, bl.Vb, bl.Ub, bl.Rb, bl.jp, bl.Vt, bl.Bmt, bl.Upt, bl.Jp);
+                n, sh.nt, mode, bl.ok, bl.lds_total, bl.ws_total, bl.c.J, bl.c.JT, bl.c.Dm, bl.c.Dinv, bl.Ta, bl.Am, bl.Hk, bl.Bb, bl.Vb, bl.Ub, bl.Rb, bl.jp, bl.Vt, bl.Bmt, bl.Upt, bl.Jp);
     if (!bl.ok) return 0;
     const size_t lds = sizeof(double) * (CG_TAB_DOUBLES + (size_t)bl.lds_total);
-    const int chunk = std::min(B, c->cu_count * per_cu * cg_env_int("CG_BIG_ROUNDS", 4));
-    if ((rc = ensure_ws(c, sizeof(double) * ((size_t)bl.ws_total * chunk + 8)))) return rc;
-    auto go = [&](auto ntc) -> int {
-        constexpr int NT = decltype(ntc)::value;
-        if (int r = set_lds(c, k_gradlap_big<D, HS, HT, NT>, lds)) return r;
-        for (int w0 = 0; w0 < B; w0 += chunk)
-            hipLaunchKernelGGL((k_gradlap_big<D, HS, HT, NT>), dim3(std::min(chunk, B - w0)), dim3(NT), lds, c->stream, m, (const double*)c->d_theta,
+    return cg_with_nt_equal<256, 512>(sh.nt, [&](auto ntc) -> int {
+        constexpr int NT = ntc;
+        return cg_launch_chunked(c, k_gradlap_big<D, HS, HT, NT>, lds, bl.ws_total, 8, sh.chunk, B, [&](int grid, int w0) {
+            hipLaunchKernelGGL((k_gradlap_big<D, HS, HT, NT>), dim3(grid), dim3(NT), lds, c->stream, m, (const double*)c->d_theta,
                                (const double*)c->d_spk, (const double*)c->d_tab, x, sidx, B, w0, mode, v, grad, lap, (double*)c->ws, bl);
-        return 0;
-    };
-    if ((rc = bnt == 256 ? go(std::integral_constant<int, 256>{}) : go(std::integral_constant<int, 512>{}))) return rc;
-    return 1;
+        });
+    });
 }
 
 // Both at once for the optimisation step (src/VMC.py:35 and the jacrev of main.py:278 on the same walkers): the set-up -- flow, Jacobian,
@@ -157,30 +151,22 @@ int cg_big_grad_lap_scores(cg_ctx* c, const CgDev& m, const double* x, const int
     constexpr int D = 2, HS = 16, HT = 16;
     typedef CgBig<D, HS, HT> Big;
     if (c->dim != D || c->hs != HS || c->ht != HT || (mode != 1 && mode != 2) || !v || c->n <= 16) return 0;
-    int rc;
+    if (cg_tune::big() == 0 || cg_tune::big_lap() == 0 || cg_tune::big_fused() == 0) return 0;
     const int n = c->n;
-    if (cg_env_int("CG_BIG", 1) == 0 || cg_env_int("CG_BIG_LAP", 1) == 0 || cg_env_int("CG_BIG_FUSED", 1) == 0) return 0;
-    const int bnt = cg_env_int("CG_BIG_NT", n * D <= 64 ? 256 : 512);
-    const int per_cu = bnt == 256 ? cg_env_int("CG_BIG_PER_CU", 2) : 1;
-    const size_t capb = (size_t)cg_env_int("CG_BIG_LDS_KB", per_cu == 2 ? 79 : 159) * 1024;
-    const auto lg = Big::layout_gradlap(n, bnt, mode, capb / sizeof(double) - CG_TAB_DOUBLES);
-    const auto ls = Big::layout_scores(n, bnt, capb / sizeof(double) - CG_TAB_DOUBLES);
+    const CgBigShape sh = big_shape(c, D, B);
+    const auto lg = Big::layout_gradlap(n, sh.nt, mode, sh.cap);
+    const auto ls = Big::layout_scores(n, sh.nt, sh.cap);
     if (!lg.ok || !ls.ok) return 0;
     const auto st = Big::stash_layout(n);
     const size_t lds = sizeof(double) * (CG_TAB_DOUBLES + (size_t)std::max(lg.lds_total, ls.lds_total));
     const size_t per_wg = (size_t)lg.ws_total + st.total + ls.ws_total;
-    const int chunk = std::min(B, c->cu_count * per_cu * cg_env_int("CG_BIG_ROUNDS", 4));
-    if ((rc = ensure_ws(c, sizeof(double) * (per_wg * chunk + 8)))) return rc;
-    auto go = [&](auto ntc) -> int {
-        constexpr int NT = decltype(ntc)::value;
-        if (int r = set_lds(c, k_gradlap_scores_big<D, HS, HT, NT>, lds)) return r;
-        for (int w0 = 0; w0 < B; w0 += chunk)
-            hipLaunchKernelGGL((k_gradlap_scores_big<D, HS, HT, NT>), dim3(std::min(chunk, B - w0)), dim3(NT), lds, c->stream, m, (const double*)c->d_theta,
+    return cg_with_nt_equal<256, 512>(sh.nt, [&](auto ntc) -> int {
+        constexpr int NT = ntc;
+        return cg_launch_chunked(c, k_gradlap_scores_big<D, HS, HT, NT>, lds, per_wg, 8, sh.chunk, B, [&](int grid, int w0) {
+            hipLaunchKernelGGL((k_gradlap_scores_big<D, HS, HT, NT>), dim3(grid), dim3(NT), lds, c->stream, m, (const double*)c->d_theta,
                                (const double*)c->d_spk, (const double*)c->d_tab, x, sidx, B, w0, mode, v, grad, lap, score, (double*)c->ws, lg, ls, st);
-        return 0;
-    };
-    if ((rc = bnt == 256 ? go(std::integral_constant<int, 256>{}) : go(std::integral_constant<int, 512>{}))) return rc;
-    return 1;
+        });
+    });
 }
 
 #if defined(CG_STAMPS)

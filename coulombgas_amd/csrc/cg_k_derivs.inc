@@ -90,126 +90,91 @@ __global__ void __launch_bounds__(NT, NT <= 256 ? 2 : WPE) k_param_vjp(CgDev m, 
                                        score + (size_t)w * P * 2, ws + (size_t)blockIdx.x * ws_per_walker, lds, lay);
 }
 
-#ifndef CG_LAP_BIG_LDS_BYTES
-#define CG_LAP_BIG_LDS_BYTES (156 * 1024)
-#endif
+typedef CG_CFG_LIST(CG_UNIT_CONFIGS) CgUnitConfigs;
+
 int CG_UNIT_NAME(grad_lap)(cg_ctx* c, const CgDev& m, const double* x, const int* sidx, int B, int mode, const double* v,
                            double* grad, double* lap) {
-    int rc; bool launched = false;
-    const int n = c->n;
-    struct { const void* dev; } ax{x}, as{sidx}, av{v}; struct { void* dev; } ag{grad}, al{lap};
-#define CG_X(D, HS, HT)                                                                                              \
-    if (!launched && c->dim == D && c->hs == HS && c->ht == HT) {                                                   \
-        /* everything in LDS at half a CU (two workgroups of 256 threads per CU = 2 waves per SIMD)? */              \
-        auto dl = CgLap<D, HS, HT>::layout(n, 256, mode, (size_t)CG_LAP_LDS_BYTES / sizeof(double) - CG_TAB_DOUBLES); \
-        if (dl.all_lds && dl.th_lds) {                                                                              \
-            const size_t lds = sizeof(double) * (CG_TAB_DOUBLES + (size_t)dl.lds_total);                            \
-            if ((rc = ensure_ws(c, 64))) return rc;                                                                 \
-            if ((rc = set_lds(c, k_grad_lap2<D, HS, HT, true, 256>, lds))) return rc;                               \
-            hipLaunchKernelGGL((k_grad_lap2<D, HS, HT, true, 256>), dim3(B), dim3(256), lds, c->stream, m, (const double*)c->d_theta, (const double*)c->d_spk, (const double*)c->d_tab, (const double*)ax.dev, \
-                               (const int*)as.dev, B, 0, mode, (const double*)av.dev, (double*)ag.dev, (double*)al.dev, \
-                               (double*)c->ws, dl);                                                                 \
-        } else if (D == 2 && HS == 16 && HT == 16 && mode != 0 &&                                                   \
-                   (rc = cg_big_grad_lap(c, m, (const double*)ax.dev, (const int*)as.dev, B, mode, (const double*)av.dev, (double*)ag.dev, (double*)al.dev)) != 0) { \
-            if (rc < 0) return rc;       /* larger systems, Hutchinson modes: the planned kernel (cg_k_big.hip) */   \
-        } else {                                                                                                    \
-            /* larger systems (exact mode, other configurations): the first generation -- the rest in the workgroup's HBM workspace slot */ \
-            const int nt = cg_env_int("CG_LAP_NT", n * D <= 64 ? 256 : 512);                                            \
-            const size_t budget = (size_t)cg_env_int("CG_LAP_LDS_KB", CG_LAP_BIG_LDS_BYTES / 1024) * 1024;              \
-            dl = CgLap<D, HS, HT>::layout(n, nt, mode, budget / sizeof(double) - CG_TAB_DOUBLES);                       \
-            const size_t lds = sizeof(double) * (CG_TAB_DOUBLES + (size_t)dl.lds_total);                                \
-            const int fit = (int)std::max<size_t>(1, (size_t)(160 * 1024) / (lds + 512));                               \
-            const int per_cu = cg_env_int("CG_LAP_PER_CU", std::min(fit, 2));                                           \
-            const int chunk = std::min(B, c->cu_count * per_cu);      /* (a slot per walker and ONE launch measured no faster) */ \
-            if ((rc = ensure_ws(c, sizeof(double) * ((size_t)dl.ws_total * chunk + 8)))) return rc;                     \
-            auto go = [&](auto ntc) -> int {                                                                            \
-                constexpr int NT = decltype(ntc)::value;                                                                \
-                if (int r = set_lds(c, k_grad_lap2<D, HS, HT, false, NT>, lds)) return r;                               \
-                for (int w0 = 0; w0 < B; w0 += chunk)                                                                   \
-                    hipLaunchKernelGGL((k_grad_lap2<D, HS, HT, false, NT>), dim3(std::min(chunk, B - w0)), dim3(NT), lds, c->stream, m, (const double*)c->d_theta, (const double*)c->d_spk, (const double*)c->d_tab, (const double*)ax.dev, \
-                                       (const int*)as.dev, B, w0, mode, (const double*)av.dev, (double*)ag.dev, (double*)al.dev, \
-                                       (double*)c->ws, dl);                                                             \
-                return 0;                                                                                               \
-            };                                                                                                          \
-            if ((rc = nt == 256 ? go(std::integral_constant<int, 256>{}) : go(std::integral_constant<int, 512>{}))) return rc; \
-        }                                                                                                           \
-        launched = true;                                                                                            \
-    }
-    CG_UNIT_CONFIGS(CG_X)
-#undef CG_X
-    return launched ? 1 : 0;
+    return cg_with_config<CgUnitConfigs>(c->dim, c->hs, c->ht, [&](auto cfg) -> int {
+        constexpr int D = cfg.D, HS = cfg.HS, HT = cfg.HT;
+        int rc;
+        const int n = c->n;
+        // everything in LDS at half a CU (two workgroups of 256 threads per CU = 2 waves per SIMD)?
+        auto dl = CgLap<D, HS, HT>::layout(n, 256, mode, (size_t)CG_LAP_LDS_BYTES / sizeof(double) - CG_TAB_DOUBLES);
+        if (dl.all_lds && dl.th_lds) {
+            const size_t lds = sizeof(double) * (CG_TAB_DOUBLES + (size_t)dl.lds_total);
+            if ((rc = ensure_ws(c, 64))) return rc;
+            if ((rc = set_lds(c, k_grad_lap2<D, HS, HT, true, 256>, lds))) return rc;
+            hipLaunchKernelGGL((k_grad_lap2<D, HS, HT, true, 256>), dim3(B), dim3(256), lds, c->stream, m, (const double*)c->d_theta, (const double*)c->d_spk,
+                               (const double*)c->d_tab, x, sidx, B, 0, mode, v, grad, lap, (double*)c->ws, dl);
+            return 1;
+        }
+        // larger systems, Hutchinson modes: the planned kernel (cg_k_big.hip)
+        if (D == 2 && HS == 16 && HT == 16 && mode != 0 && (rc = cg_big_grad_lap(c, m, x, sidx, B, mode, v, grad, lap)) != 0) return rc;
+        // larger systems (exact mode, other configurations): the first generation -- the rest in the workgroup's HBM workspace slot
+        const int nt = cg_tune::lap_nt(n, D);
+        dl = CgLap<D, HS, HT>::layout(n, nt, mode, (size_t)cg_tune::lap_lds_kb() * 1024 / sizeof(double) - CG_TAB_DOUBLES);
+        const size_t lds = sizeof(double) * (CG_TAB_DOUBLES + (size_t)dl.lds_total);
+        const int fit = (int)std::max<size_t>(1, (size_t)(160 * 1024) / (lds + 512));
+        const int chunk = std::min(B, c->cu_count * cg_tune::lap_per_cu(fit));      // (a slot per walker and ONE launch measured no faster)
+        return cg_with_nt_equal<256, 512>(nt, [&](auto ntc) -> int {
+            constexpr int NT = ntc;
+            return cg_launch_chunked(c, k_grad_lap2<D, HS, HT, false, NT>, lds, dl.ws_total, 8, chunk, B, [&](int grid, int w0) {
+                hipLaunchKernelGGL((k_grad_lap2<D, HS, HT, false, NT>), dim3(grid), dim3(NT), lds, c->stream, m, (const double*)c->d_theta, (const double*)c->d_spk,
+                                   (const double*)c->d_tab, x, sidx, B, w0, mode, v, grad, lap, (double*)c->ws, dl);
+            });
+        });
+    });
 }
 
-#ifndef CG_VJP_BIG_LDS_BYTES
-#define CG_VJP_BIG_LDS_BYTES (156 * 1024)
-#endif
 // scores of B walkers into score (B x P x 2) by the first-generation kernel: 1 launched, 0 not this unit, < 0 error
 int CG_UNIT_NAME(param_vjp)(cg_ctx* c, const CgDev& m, const double* x, const int* sidx, int B, double* score) {
-    int rc; bool launched = false;
-    const int n = c->n;
-    struct { const void* dev; } ax{x}, as{sidx}; struct { void* dev; } asc{score};
-#define CG_X(D, HS, HT)                                                                                               \
-    if (!launched && c->dim == D && c->hs == HS && c->ht == HT) {                                                    \
-        const size_t wsw = CgDerivs<D, HS, HT>::ws_doubles(n);                                                       \
-        auto dl = CgDerivs<D, HS, HT>::layout(n, 256);                                                               \
-        if (dl.vjp_fast) {      /* small systems: the arena / the inverses fit a share of the CU's LDS: 256 threads, 2-3 workgroups per CU */ \
-            const size_t lds = sizeof(double) * (CG_TAB_DOUBLES + CgDerivs<D, HS, HT>::lds_doubles(n, 256) + CgDerivs<D, HS, HT>::vjp_lds_doubles(dl)); \
-            const int chunk = std::min(B, c->cu_count * 2 * CG_DERIV_WAVES_OF(D));                                   \
-            if ((rc = ensure_ws(c, sizeof(double) * wsw * chunk))) return rc;                                        \
-            if ((rc = set_lds(c, k_param_vjp<D, HS, HT, 256>, lds))) return rc;                                      \
-            for (int w0 = 0; w0 < B; w0 += chunk)                                                                    \
-                hipLaunchKernelGGL((k_param_vjp<D, HS, HT, 256>), dim3(std::min(chunk, B - w0)), dim3(256), lds, c->stream, m, (const double*)c->d_theta, (const double*)c->d_spk, (const double*)c->d_tab, (const double*)ax.dev, \
-                                   (const int*)as.dev, B, w0, (double*)asc.dev, (double*)c->ws, wsw, dl);            \
-        } else {                /* larger systems: the inverses in place on an LDS copy where it fits, chunked launches */ \
-            const int nt = cg_env_int("CG_VJP_NT", 512);                                                                \
-            const size_t budget = (size_t)cg_env_int("CG_VJP_LDS_KB", CG_VJP_BIG_LDS_BYTES / 1024) * 1024;              \
-            dl = CgDerivs<D, HS, HT>::layout(n, nt, budget);                                                            \
-            const size_t lds = sizeof(double) * (CG_TAB_DOUBLES + CgDerivs<D, HS, HT>::lds_doubles(n, nt) + CgDerivs<D, HS, HT>::vjp_lds_doubles(dl)); \
-            const int fit = (int)std::max<size_t>(1, (size_t)(160 * 1024) / (lds + 512));                               \
-            const int per_cu = cg_env_int("CG_VJP_PER_CU", std::min(fit, 2));                                           \
-            const int chunk = std::min(B, c->cu_count * per_cu);                                                        \
-            if ((rc = ensure_ws(c, sizeof(double) * wsw * chunk))) return rc;                                        \
-            auto go = [&](auto ntc, auto wpec) -> int {                                                                 \
-                constexpr int NT = decltype(ntc)::value, WPE = decltype(wpec)::value;                                   \
-                if (int r = set_lds(c, k_param_vjp<D, HS, HT, NT, WPE>, lds)) return r;                                 \
-                for (int w0 = 0; w0 < B; w0 += chunk)                                                                    \
-                    hipLaunchKernelGGL((k_param_vjp<D, HS, HT, NT, WPE>), dim3(std::min(chunk, B - w0)), dim3(NT), lds, c->stream, m, (const double*)c->d_theta, (const double*)c->d_spk, (const double*)c->d_tab, (const double*)ax.dev, \
-                                       (const int*)as.dev, B, w0, (double*)asc.dev, (double*)c->ws, wsw, dl);            \
-                return 0;                                                                                               \
-            };                                                                                                          \
-            const bool occ = cg_env_int("CG_VJP_OCC", n * D > 64 ? 1 : 0) != 0 && nt == 512 && per_cu >= 2;   /* two workgroups per CU (128 VGPRs) */ \
-            if ((rc = nt == 256 ? go(std::integral_constant<int, 256>{}, std::integral_constant<int, 1>{})              \
-                      : occ ? go(std::integral_constant<int, 512>{}, std::integral_constant<int, 4>{})                  \
-                            : go(std::integral_constant<int, 512>{}, std::integral_constant<int, 1>{}))) return rc;     \
-        }                                                                                                            \
-        launched = true;                                                                                             \
-    }
-    CG_UNIT_CONFIGS(CG_X)
-#undef CG_X
-    return launched ? 1 : 0;
+    return cg_with_config<CgUnitConfigs>(c->dim, c->hs, c->ht, [&](auto cfg) -> int {
+        constexpr int D = cfg.D, HS = cfg.HS, HT = cfg.HT;
+        typedef CgDerivs<D, HS, HT> Dv;
+        const int n = c->n;
+        const size_t wsw = Dv::ws_doubles(n);
+        auto dl = Dv::layout(n, 256);
+        if (dl.vjp_fast) {      // small systems: the arena / the inverses fit a share of the CU's LDS: 256 threads, 2-3 workgroups per CU
+            const size_t lds = sizeof(double) * (CG_TAB_DOUBLES + Dv::lds_doubles(n, 256) + Dv::vjp_lds_doubles(dl));
+            const int chunk = std::min(B, c->cu_count * 2 * CG_DERIV_WAVES_OF(D));
+            return cg_launch_chunked(c, k_param_vjp<D, HS, HT, 256>, lds, wsw, 0, chunk, B, [&](int grid, int w0) {
+                hipLaunchKernelGGL((k_param_vjp<D, HS, HT, 256>), dim3(grid), dim3(256), lds, c->stream, m, (const double*)c->d_theta, (const double*)c->d_spk,
+                                   (const double*)c->d_tab, x, sidx, B, w0, score, (double*)c->ws, wsw, dl);
+            });
+        }
+        // larger systems: the inverses in place on an LDS copy where it fits, chunked launches
+        const int nt = cg_tune::vjp_nt();
+        dl = Dv::layout(n, nt, (size_t)cg_tune::vjp_lds_kb() * 1024);
+        const size_t lds = sizeof(double) * (CG_TAB_DOUBLES + Dv::lds_doubles(n, nt) + Dv::vjp_lds_doubles(dl));
+        const int fit = (int)std::max<size_t>(1, (size_t)(160 * 1024) / (lds + 512));
+        const int per_cu = cg_tune::vjp_per_cu(fit);
+        const int chunk = std::min(B, c->cu_count * per_cu);
+        auto go = [&](auto ntc, auto wpec) -> int {
+            constexpr int NT = ntc, WPE = wpec;
+            return cg_launch_chunked(c, k_param_vjp<D, HS, HT, NT, WPE>, lds, wsw, 0, chunk, B, [&](int grid, int w0) {
+                hipLaunchKernelGGL((k_param_vjp<D, HS, HT, NT, WPE>), dim3(grid), dim3(NT), lds, c->stream, m, (const double*)c->d_theta, (const double*)c->d_spk,
+                                   (const double*)c->d_tab, x, sidx, B, w0, score, (double*)c->ws, wsw, dl);
+            });
+        };
+        const bool occ = cg_tune::vjp_occ(n, D) != 0 && nt == 512 && per_cu >= 2;       // two workgroups per CU (128 VGPRs): 512 threads only
+        return cg_with_nt_equal<256, 512>(nt, [&](auto ntc) -> int {
+            if constexpr (ntc == 512) { if (occ) return go(ntc, std::integral_constant<int, 4>{}); }
+            return go(ntc, std::integral_constant<int, 1>{});
+        });
+    });
 }
 
 // scores of B walkers into score (B x P x 2): 1 launched, 0 this unit / this size is served by k_param_vjp, < 0 error
 int CG_UNIT_NAME(scores)(cg_ctx* c, const CgDev& m, const double* x, const int* sidx, int B, double* score) {
-    int rc; bool launched = false;
-    const int n = c->n, nt = 256;
-    struct { const void* dev; } ax{x}, as{sidx}; struct { void* dev; } asc{score};
-#define CG_X(D, HS, HT)                                                                                              \
-    if (!launched && c->dim == D && c->hs == HS && c->ht == HT) {                                                   \
-        if (!(HS == 16 && HT == 16)) return 0;                                                                      \
-        const auto dl = CgScore<D, HS, HT>::layout(n, nt, (size_t)CG_SCORE_LDS_BYTES / sizeof(double) - CG_TAB_DOUBLES); \
-        if (!dl.ok) {          /* larger systems: the planned kernel (cg_big.hpp) */                               \
-            if (D == 2) return cg_big_scores(c, m, (const double*)ax.dev, (const int*)as.dev, B, (double*)asc.dev);  /* (cg_k_big.hip) */ \
-            return 0;                                                                                               \
-        } else {                                                                                                    \
-        const size_t lds = sizeof(double) * (CG_TAB_DOUBLES + (size_t)dl.total);                                    \
-        if ((rc = set_lds(c, k_scores<D, HS, HT>, lds))) return rc;                                                 \
-        hipLaunchKernelGGL((k_scores<D, HS, HT>), dim3(B), dim3(nt), lds, c->stream, m, (const double*)c->d_theta, (const double*)c->d_spk, \
-                           (const double*)c->d_tab, (const double*)ax.dev, (const int*)as.dev, B, (double*)asc.dev, dl); \
-        launched = true;                                                                                            \
-        }                                                                                                           \
-    }
-    CG_UNIT_CONFIGS(CG_X)
-#undef CG_X
-    return launched ? 1 : 0;
+    return cg_with_config<CgUnitConfigs>(c->dim, c->hs, c->ht, [&](auto cfg) -> int {
+        constexpr int D = cfg.D, HS = cfg.HS, HT = cfg.HT, nt = 256;
+        if (!(HS == 16 && HT == 16)) return 0;
+        const auto dl = CgScore<D, HS, HT>::layout(c->n, nt, (size_t)CG_SCORE_LDS_BYTES / sizeof(double) - CG_TAB_DOUBLES);
+        if (!dl.ok) return D == 2 ? cg_big_scores(c, m, x, sidx, B, score) : 0;     // larger systems: the planned kernel (cg_k_big.hip)
+        const size_t lds = sizeof(double) * (CG_TAB_DOUBLES + (size_t)dl.total);
+        if (int rc = set_lds(c, k_scores<D, HS, HT>, lds)) return rc;
+        hipLaunchKernelGGL((k_scores<D, HS, HT>), dim3(B), dim3(nt), lds, c->stream, m, (const double*)c->d_theta, (const double*)c->d_spk,
+                           (const double*)c->d_tab, x, sidx, B, score, dl);
+        return 1;
+    });
 }

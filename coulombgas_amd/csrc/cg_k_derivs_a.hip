@@ -202,7 +202,7 @@ __global__ void __launch_bounds__(256, 2) k_grad_lap2_scores(CgDev m, const doub
 static int small_grad_lap_scores(cg_ctx* c, const CgDev& m, const double* x, const int* sidx, int B, int mode, const double* v, double* grad, double* lap,
                                  double* score) {
     constexpr int D = 2, HS = 16, HT = 16;
-    if (c->dim != D || c->hs != HS || c->ht != HT || (mode != 1 && mode != 2) || !v || cg_env_int("CG_SMALL_FUSED", 1) == 0) return 0;
+    if (c->dim != D || c->hs != HS || c->ht != HT || (mode != 1 && mode != 2) || !v || cg_tune::small_fused() == 0) return 0;
     int rc;
     const int n = c->n;
     const auto lg = CgLap<D, HS, HT>::layout(n, 256, mode, (size_t)CG_LAP_LDS_BYTES / sizeof(double) - CG_TAB_DOUBLES);
@@ -210,8 +210,7 @@ static int small_grad_lap_scores(cg_ctx* c, const CgDev& m, const double* x, con
     if (!(lg.all_lds && lg.th_lds) || !ls.ok) return 0;
     const auto st = CgScore<D, HS, HT>::stash_of(ls);
     const size_t lds = sizeof(double) * (CG_TAB_DOUBLES + (size_t)std::max(lg.lds_total, ls.total));
-    const int chunk = std::min(B, cg_env_int("CG_SMALL_FUSED_CHUNK", 16384));        // (77 KB of stash per walker in flight: 1.2 GB at most)
-    if ((rc = ensure_ws(c, sizeof(double) * ((size_t)st.total * chunk + 64)))) return rc;
+    const int chunk = std::min(B, cg_tune::small_fused_chunk());        // (77 KB of stash per walker in flight)
     if (c->lay_tag != 1) {                     // the score layout, once per context, where the kernel reads it
         if (!c->d_lay && hipMalloc(&c->d_lay, 4096) != hipSuccess) CG_FAIL(c, CG_ERR_HIP, "cg_grad_laplacian_scores: device allocation failed");
         static_assert(sizeof(ls) + sizeof(st) <= 2048, "layout buffer");
@@ -220,12 +219,11 @@ static int small_grad_lap_scores(cg_ctx* c, const CgDev& m, const double* x, con
         CG_HIP(c, hipStreamSynchronize(c->stream));
         c->lay_tag = 1;
     }
-    if ((rc = set_lds(c, k_grad_lap2_scores<D, HS, HT>, lds))) return rc;
-    for (int w0 = 0; w0 < B; w0 += chunk)
-        hipLaunchKernelGGL((k_grad_lap2_scores<D, HS, HT>), dim3(std::min(chunk, B - w0)), dim3(256), lds, c->stream, m, (const double*)c->d_theta, (const double*)c->d_spk,
-                       (const double*)c->d_tab, x, sidx, B, w0, mode, v, grad, lap, score, (double*)c->ws, lg, (const CgScore<D, HS, HT>::Lay*)c->d_lay,
-                       (const CgLap<D, HS, HT>::Stash*)((const char*)c->d_lay + 2048), st.total);
-    return 1;
+    return cg_launch_chunked(c, k_grad_lap2_scores<D, HS, HT>, lds, st.total, 64, chunk, B, [&](int grid, int w0) {
+        hipLaunchKernelGGL((k_grad_lap2_scores<D, HS, HT>), dim3(grid), dim3(256), lds, c->stream, m, (const double*)c->d_theta, (const double*)c->d_spk,
+                           (const double*)c->d_tab, x, sidx, B, w0, mode, v, grad, lap, score, (double*)c->ws, lg, (const CgScore<D, HS, HT>::Lay*)c->d_lay,
+                           (const CgLap<D, HS, HT>::Stash*)((const char*)c->d_lay + 2048), st.total);
+    });
 }
 
 int cg_big_grad_lap_scores(cg_ctx* c, const CgDev& m, const double* x, const int* sidx, int B, int mode, const double* v, double* grad, double* lap,
@@ -257,13 +255,11 @@ int cg_grad_laplacian(cg_ctx* c, const double* x, const int32_t* sidx, int B, in
         return finish(c);
     }
     const CgDev m = make_dev(c);
-    bool launched = false;
     if ((rc = cg_derivs_a_grad_lap(c, m, (const double*)ax.dev, (const int*)as.dev, B, mode, (const double*)av.dev, (double*)ag.dev,
                                    (double*)al.dev)) < 0) return rc;
     if (rc == 0 && (rc = cg_derivs_b_grad_lap(c, m, (const double*)ax.dev, (const int*)as.dev, B, mode, (const double*)av.dev,
                                               (double*)ag.dev, (double*)al.dev)) < 0) return rc;
-    launched = rc == 1;
-    if (!launched) CG_FAIL(c, CG_ERR_UNSUPPORTED, "cg_grad_laplacian: configuration not instantiated");
+    if (rc != 1) CG_FAIL(c, CG_ERR_UNSUPPORTED, "cg_grad_laplacian: configuration not instantiated");
     for (Arg* a : all) if ((rc = unstage(c, *a))) return rc;
     return finish(c);
 }

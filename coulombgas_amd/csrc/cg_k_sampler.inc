@@ -131,65 +131,37 @@ __global__ void __launch_bounds__(MAXT, (MAXT <= 256 ? CG_WAVES_PER_EU : 1)) k_m
 }
 
 
+typedef CG_CFG_LIST(CG_UNIT_CONFIGS) CgUnitConfigs;
+typedef CG_CFG_LIST(CG_UNIT_SPECIALS) CgUnitSpecials;
+
 int CG_UNIT_NAME(logpsi)(cg_ctx* c, int nt, size_t lds, const CgDev& m, const double* x, const int* sidx, int B, int mode,
                          double* logphi, double* hld, double* logpsi_out, double* logp_out, double* z_out, double* J_out) {
-    int rc; bool launched = false;
-    struct { const void* dev; } ax{x}, as{sidx}; struct { void* dev; } a1{logphi}, a2{hld}, a3{logpsi_out}, a4{logp_out}, a5{z_out}, a6{J_out};
-#define CG_X(D, HS, HT)                                                                                              \
-    if (!launched && c->dim == D && c->hs == HS && c->ht == HT) {                                                   \
-        if (nt <= 256) {                                                                                             \
-            if ((rc = set_lds(c, k_logpsi<D, HS, HT, 256>, lds))) return rc;                                         \
-            hipLaunchKernelGGL((k_logpsi<D, HS, HT, 256>), dim3(B), dim3(nt), lds, c->stream, m, (const double*)c->d_theta, (const double*)c->d_spk, (const double*)c->d_tab, (const double*)ax.dev, \
-                               (const int*)as.dev, B, mode, (double*)a1.dev, (double*)a2.dev, (double*)a3.dev,       \
-                               (double*)a4.dev, (double*)a5.dev, (double*)a6.dev);                                   \
-        } else {                                                                                                     \
-            if ((rc = set_lds(c, k_logpsi<D, HS, HT, 1024>, lds))) return rc;                                        \
-            hipLaunchKernelGGL((k_logpsi<D, HS, HT, 1024>), dim3(B), dim3(nt), lds, c->stream, m, (const double*)c->d_theta, (const double*)c->d_spk, (const double*)c->d_tab, (const double*)ax.dev, \
-                               (const int*)as.dev, B, mode, (double*)a1.dev, (double*)a2.dev, (double*)a3.dev,       \
-                               (double*)a4.dev, (double*)a5.dev, (double*)a6.dev);                                   \
-        }                                                                                                            \
-        launched = true;                                                                                             \
-    }
-    CG_UNIT_CONFIGS(CG_X)
-#undef CG_X
-    return launched ? 1 : 0;
+    return cg_with_config<CgUnitConfigs>(c->dim, c->hs, c->ht, [&](auto cfg) -> int {
+        return cg_with_nt_upto<256, 1024>(nt, [&](auto ntc) -> int {
+            constexpr int D = cfg.D, HS = cfg.HS, HT = cfg.HT, MAXT = ntc;
+            if (int rc = set_lds(c, k_logpsi<D, HS, HT, MAXT>, lds)) return rc;
+            hipLaunchKernelGGL((k_logpsi<D, HS, HT, MAXT>), dim3(B), dim3(nt), lds, c->stream, m, (const double*)c->d_theta, (const double*)c->d_spk,
+                               (const double*)c->d_tab, x, sidx, B, mode, logphi, hld, logpsi_out, logp_out, z_out, J_out);
+            return 1;
+        });
+    });
 }
 
 int CG_UNIT_NAME(mcmc)(cg_ctx* c, int nt, size_t lds, const CgDev& m, double* x, const int* sidx, int B, int mc_steps, double mc_stddev,
                        uint64_t seed, uint64_t walker_offset, const double* noise, const double* unif, double* logp_out) {
-    int rc; bool launched = false;
-    struct { void* dev; } ax{x}, al{logp_out}; struct { const void* dev; } as{sidx}, an{noise}, au{unif};
-#define CG_X(D, HS, HT, NS, NT)                                                                                     \
-    if (!launched && c->dim == D && c->hs == HS && c->ht == HT && c->n == NS && nt == NT) {                        \
-        if ((rc = set_lds(c, k_mcmc<D, HS, HT, NT, NS>, lds))) return rc;                                           \
-        hipLaunchKernelGGL((k_mcmc<D, HS, HT, NT, NS>), dim3(B), dim3(nt), lds, c->stream, m, (const double*)c->d_theta, (const double*)c->d_spk, (const double*)c->d_tab, (double*)ax.dev,     \
-                           (const int*)as.dev, B, mc_steps, mc_stddev, seed, walker_offset,                         \
-                           (const double*)an.dev, (const double*)au.dev, (double*)al.dev, c->d_accept);             \
-        launched = true;                                                                                            \
-    }
-    CG_UNIT_SPECIALS(CG_X)
-#undef CG_X
-#define CG_X(D, HS, HT)                                                                                             \
-    if (!launched && c->dim == D && c->hs == HS && c->ht == HT) {                                                  \
-        if (nt <= 256) {                                                                                            \
-            if ((rc = set_lds(c, k_mcmc<D, HS, HT, 256>, lds))) return rc;                                          \
-            hipLaunchKernelGGL((k_mcmc<D, HS, HT, 256>), dim3(B), dim3(nt), lds, c->stream, m, (const double*)c->d_theta, (const double*)c->d_spk, (const double*)c->d_tab, (double*)ax.dev,     \
-                               (const int*)as.dev, B, mc_steps, mc_stddev, seed, walker_offset,                     \
-                               (const double*)an.dev, (const double*)au.dev, (double*)al.dev, c->d_accept);         \
-        } else if (nt <= 512) {     /* (an instantiation of its own: 256 registers per lane instead of the 128 of the 1024-thread one) */ \
-            if ((rc = set_lds(c, k_mcmc<D, HS, HT, 512>, lds))) return rc;                                          \
-            hipLaunchKernelGGL((k_mcmc<D, HS, HT, 512>), dim3(B), dim3(nt), lds, c->stream, m, (const double*)c->d_theta, (const double*)c->d_spk, (const double*)c->d_tab, (double*)ax.dev,     \
-                               (const int*)as.dev, B, mc_steps, mc_stddev, seed, walker_offset,                     \
-                               (const double*)an.dev, (const double*)au.dev, (double*)al.dev, c->d_accept);         \
-        } else {                                                                                                    \
-            if ((rc = set_lds(c, k_mcmc<D, HS, HT, 1024>, lds))) return rc;                                         \
-            hipLaunchKernelGGL((k_mcmc<D, HS, HT, 1024>), dim3(B), dim3(nt), lds, c->stream, m, (const double*)c->d_theta, (const double*)c->d_spk, (const double*)c->d_tab, (double*)ax.dev,    \
-                               (const int*)as.dev, B, mc_steps, mc_stddev, seed, walker_offset,                     \
-                               (const double*)an.dev, (const double*)au.dev, (double*)al.dev, c->d_accept);         \
-        }                                                                                                           \
-        launched = true;                                                                                            \
-    }
-    CG_UNIT_CONFIGS(CG_X)
-#undef CG_X
-    return launched ? 1 : 0;
+    // MAXT: the bound the kernel is compiled for, NS: the particle number it is specialised on (0: any)
+    auto launch = [&](auto cfg, auto maxt, auto ns) -> int {
+        constexpr int D = cfg.D, HS = cfg.HS, HT = cfg.HT, MAXT = maxt, NS = ns;
+        if (int rc = set_lds(c, k_mcmc<D, HS, HT, MAXT, NS>, lds)) return rc;
+        hipLaunchKernelGGL((k_mcmc<D, HS, HT, MAXT, NS>), dim3(B), dim3(nt), lds, c->stream, m, (const double*)c->d_theta, (const double*)c->d_spk,
+                           (const double*)c->d_tab, x, sidx, B, mc_steps, mc_stddev, seed, walker_offset, noise, unif, logp_out, c->d_accept);
+        return 1;
+    };
+    if (int rc = cg_with_special<CgUnitSpecials>(c->dim, c->hs, c->ht, c->n, nt, [&](auto cfg) -> int {
+            return launch(cfg, std::integral_constant<int, cfg.NT>{}, std::integral_constant<int, cfg.N>{});
+        })) return rc;
+    // (512 threads: an instantiation of its own, 256 registers per lane instead of the 128 of the 1024-thread one)
+    return cg_with_config<CgUnitConfigs>(c->dim, c->hs, c->ht, [&](auto cfg) -> int {
+        return cg_with_nt_upto<256, 512, 1024>(nt, [&](auto ntc) -> int { return launch(cfg, ntc, std::integral_constant<int, 0>{}); });
+    });
 }

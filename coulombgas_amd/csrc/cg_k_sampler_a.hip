@@ -41,13 +41,11 @@ static int run_logpsi(cg_ctx* c, const char* fn, const double* x, const int32_t*
     const int nt = threads_of(c);
     const size_t lds = sizeof(double) * (CG_TAB_DOUBLES + c->lay.total + ((N + 1) & ~1));
     const CgDev m = make_dev(c);
-    bool launched = false;
     if ((rc = cg_sampler_a_logpsi(c, nt, lds, m, (const double*)ax.dev, (const int*)as.dev, B, mode, (double*)a1.dev, (double*)a2.dev,
                                   (double*)a3.dev, (double*)a4.dev, (double*)a5.dev, (double*)a6.dev)) < 0) return rc;
     if (rc == 0 && (rc = cg_sampler_b_logpsi(c, nt, lds, m, (const double*)ax.dev, (const int*)as.dev, B, mode, (double*)a1.dev, (double*)a2.dev,
                                              (double*)a3.dev, (double*)a4.dev, (double*)a5.dev, (double*)a6.dev)) < 0) return rc;
-    launched = rc == 1;
-    if (!launched) CG_FAIL(c, CG_ERR_UNSUPPORTED, "%s: configuration not instantiated", fn);
+    if (rc != 1) CG_FAIL(c, CG_ERR_UNSUPPORTED, "%s: configuration not instantiated", fn);
     for (Arg* a : all) if ((rc = unstage(c, *a))) return rc;
     return finish(c);
 }
@@ -101,13 +99,11 @@ int cg_mcmc(cg_ctx* c, double* x, const int32_t* sidx, int B, int mc_steps, doub
     const int nt = threads_of(c);
     const size_t lds = sizeof(double) * (CG_TAB_DOUBLES + c->lay.total + 3 * ((N + 1) & ~1) + 2);   // + x, proposal, flag, k-vectors
     const CgDev m = make_dev(c);
-    bool launched = false;
     if ((rc = cg_sampler_a_mcmc(c, nt, lds, m, (double*)ax.dev, (const int*)as.dev, B, mc_steps, mc_stddev, seed, walker_offset,
                                 (const double*)an.dev, (const double*)au.dev, (double*)al.dev)) < 0) return rc;
     if (rc == 0 && (rc = cg_sampler_b_mcmc(c, nt, lds, m, (double*)ax.dev, (const int*)as.dev, B, mc_steps, mc_stddev, seed, walker_offset,
                                            (const double*)an.dev, (const double*)au.dev, (double*)al.dev)) < 0) return rc;
-    launched = rc == 1;
-    if (!launched) CG_FAIL(c, CG_ERR_UNSUPPORTED, "cg_mcmc: configuration not instantiated");
+    if (rc != 1) CG_FAIL(c, CG_ERR_UNSUPPORTED, "cg_mcmc: configuration not instantiated");
     for (Arg* a : all) if ((rc = unstage(c, *a))) return rc;
     if ((rc = finish(c))) return rc;
     if (n_accept) return cg_mcmc_accepts(c, n_accept);

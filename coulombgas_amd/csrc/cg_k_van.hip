@@ -43,11 +43,11 @@ int cg_van_grad_par_launch(cg_ctx* c, const int* sidx_dev, int B, double* S) {
     // (short sequences with ONE sample per wave leave most lanes without a position -- n = 13, B = 8192: 3.9 ms against 3.7 ms sequential --
     // so up to n = 33 several samples share a wave: 1.36 ms at n = 13, 1.35 ms against 1.40 ms at n = 29, B = 2048)
     if (!CgVanPar::serves(m)) return 0;
-    if (m.n <= cg_env_int("CG_VAN_PACKED_MAXN", 33) && cg_env_int("CG_VAN_PACKED", 1) != 0 && cg_env_int("CG_VAN_PAR", 1) != 0) {
+    if (m.n <= cg_tune::van_packed_maxn() && cg_tune::van_packed() != 0 && cg_tune::van_par(true, m.n) != 0) {
         // short sequences: 64 / (n - 1) samples per wave
         const int per = CgVanPar::packed_samples(m.n);
         const size_t wbp = sizeof(double) * (size_t)CgVanPar::packed_wave_doubles(m.n), tbp = sizeof(double) * CG_TAB_DOUBLES;
-        int wv = cg_env_int("CG_VAN_PAR_WAVES", 0);
+        int wv = cg_tune::van_par_waves();
         if (wv <= 0) { const int per_cu = (int)std::min<size_t>(4, (160 * 1024 - 2 * tbp) / wbp); wv = per_cu >= 4 ? 4 : per_cu >= 2 ? 2 : per_cu; }
         if (per >= 2 && wv >= 1 && tbp + wv * wbp <= 160 * 1024) {
             int rc;
@@ -61,9 +61,9 @@ int cg_van_grad_par_launch(cg_ctx* c, const int* sidx_dev, int B, double* S) {
             return 1;
         }
     }
-    if (cg_env_int("CG_VAN_PAR", m.n >= 20 ? 1 : 0) == 0) return 0;
+    if (cg_tune::van_par(false, m.n) == 0) return 0;
     const size_t wb = sizeof(double) * (size_t)CgVanPar::wave_doubles(m.n), tb = sizeof(double) * CG_TAB_DOUBLES;
-    int waves = cg_env_int("CG_VAN_PAR_WAVES", 0);
+    int waves = cg_tune::van_par_waves();
     if (waves <= 0) {                       // as many waves per CU as LDS allows (<= 4: one per SIMD), in workgroups that tile the CU
         const int per_cu = (int)std::min<size_t>(4, (160 * 1024 - 2 * tb) / wb);
         if (per_cu < 1) return 0;

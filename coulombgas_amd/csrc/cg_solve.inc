@@ -85,7 +85,7 @@ static int fisher_real_launch(cg_ctx* c, const double* S, int B, int P, double* 
     // a few rounds of workgroups per CU (P = 5907: 1128 blocks on 256 CUs = 4.4 -> 5 rounds, one of them 40 % full): four batch slices give
     // 17.6 rounds of quarter-length blocks; 6.9 -> 5.9 ms at B = 8192 with the fixed-order sum of the partial matrices included
     if (nsl == 1 && blocks >= c->cu_count && blocks < 8 * c->cu_count && B >= 4096) nsl = 4;
-    { const int f = cg_env_int("CG_FISHER_SLICES", 0); if (f > 0) nsl = f; }
+    { const int f = cg_tune::fisher_slices(); if (f > 0) nsl = f; }
     const int chunk = (((B + nsl - 1) / nsl) + 3) & ~3;
     if (nsl == 1) {
         hipLaunchKernelGGL(k_fisher_real, dim3(nbt, nbt, 1), dim3(256), 0, c->stream, S, B, P, chunk, 1.0 / (double)B, F);
@@ -636,7 +636,7 @@ extern "C" {
 // trailing update of the columns [cb, P) (T row blocks) with the K = kl panel at column kb: a wave per 64 x 64 block when that fills the
 // GPU, a wave per quadrant when it does not
 static void chol_trailing_update(cg_ctx* c, hipStream_t st, double* dA, int P, int kb, int kl, int cb, int T) {
-    static const int qmax = cg_env_int("CG_CHOL_QUADRANT_BLOCKS", 1024);
+    static const int qmax = cg_tune::chol_quadrant_blocks();
     if (T * (T + 1) / 2 < qmax) hipLaunchKernelGGL(k_chol_update_q, dim3(T, T), dim3(256), 0, st, dA, P, kb, kl, cb, P);
     else hipLaunchKernelGGL((k_chol_update<2, 2>), dim3((T + 3) / 4, T), dim3(256), 0, st, dA, P, kb, kl, cb, P);
 }
@@ -650,7 +650,7 @@ static int chol_factor_dev(cg_ctx* c, double* dA, int P, int* dinfo, double* din
     double* Xo_all = (double*)arena_take(c, sizeof(double) * (size_t)nouter * CG_CHOL_OUTER * CG_CHOL_OUTER);      // L_oo^-1 of every outer block
     if (Xo_out) *Xo_out = Xo_all;
     if (!Xo_all) CG_FAIL(c, CG_ERR_HIP, "Cholesky: workspace allocation failed");
-    const bool ahead = nouter > 2 && !cg_env_int("CG_CHOL_NO_LOOKAHEAD", 0);
+    const bool ahead = nouter > 2 && !cg_tune::chol_no_lookahead();
     if (ahead && !c->stream2) {
         CG_HIP(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
         CG_HIP(c, hipEventCreateWithFlags(&c->ev_a, hipEventDisableTiming));
@@ -663,7 +663,7 @@ static int chol_factor_dev(cg_ctx* c, double* dA, int P, int* dinfo, double* din
     for (int o0 = 0; o0 < P; o0 += CG_CHOL_OUTER) {
         const int oe = std::min(P, o0 + CG_CHOL_OUTER);
         double* Xo = Xo_all + (size_t)(o0 / CG_CHOL_OUTER) * CG_CHOL_OUTER * CG_CHOL_OUTER;
-        hipLaunchKernelGGL(k_chol_block, dim3(1), dim3(cg_env_int("CG_CHOL_BLOCK_NT", 1024)), CG_CHOL_BLOCK_LDS, c->stream, dA, P, o0, oe, dinfo, dinv, Xo);
+        hipLaunchKernelGGL(k_chol_block, dim3(1), dim3(cg_tune::chol_block_nt()), CG_CHOL_BLOCK_LDS, c->stream, dA, P, o0, oe, dinfo, dinv, Xo);
         if (oe >= P) break;
         const int T = (P - oe + 63) / 64;
         hipLaunchKernelGGL(k_chol_xinv, dim3(3), dim3(256), CG_CHOL_XINV_LDS, c->stream, (const double*)dA, P, o0, oe, (const double*)dinv, Xo);

@@ -4,6 +4,7 @@
 # -fsanitize=address,undefined, and the CPU tests that drive them -- all six golden sizes up to the n = 57 layouts -- run against
 # those builds.  GPU sanitizers are not available on this pool.   usage: tools/sanitize_cpu.sh [LOGFILE]
 set -e
+set -o pipefail      # the test run below is piped into tee: its exit status is the script's
 cd "$(dirname "$0")/.."
 LOG=${1:-profiles/cpu_sanitizers.log}
 python -m coulombgas_amd.build --sanitize --force
