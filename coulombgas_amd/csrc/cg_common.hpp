@@ -205,9 +205,8 @@ CG_DEVI void softplus_sigmoid(double u, double& sp, double& sg) {
     sp = fmax(u, 0.0) + fma(e - (w - 1.0), r, lg);
     sg = (u >= 0.0) ? r : e * r;
 }
-CG_DEVI double sigmoid_only(double u) {
-    const double e = cg_exp_nonpos(-fabs(u));
-    const double w = 1.0 + e;                             // in [1, 2]
+// sigmoid(u) from an exponential the caller already holds: e = e^{-|u|}, w = 1 + e in [1, 2]
+CG_DEVI double sigmoid_from_exp(double u, double e, double w) {
 #if defined(__HIP_DEVICE_COMPILE__)
     // 1/w from v_rcp_f64 + two Newton steps (no table look-up, no w = 2 special case): 5 instructions instead of 15
     double r = __builtin_amdgcn_rcp(w);
@@ -217,6 +216,10 @@ CG_DEVI double sigmoid_only(double u) {
     const double r = 1.0 / w;
 #endif
     return (u >= 0.0) ? r : e * r;
+}
+CG_DEVI double sigmoid_only(double u) {
+    const double e = cg_exp_nonpos(-fabs(u));
+    return sigmoid_from_exp(u, e, 1.0 + e);
 }
 // log(w) only, w in [1, 2]  (same table as cg_log_rcp_12, without the reciprocal)
 CG_DEVI double cg_log_12(double w) {

@@ -137,6 +137,21 @@ struct CgFast {
     struct DenseP { double w0[2], b0, b2, wacb[12], wf[4], bf; };     // primal dense layers
     struct DenseJ { double ja[4], jb[4], jc[4]; };                     // R_i W_x^T
     struct DenseU { double w0t[4]; };
+    // Single-wave sampler specialised on n = NS (k_mcmc<.., 64, NS>): sigmoid(u_ij[h]) of every pair and unit, formed by the pair-primal
+    // pass from the exponential it computes anyway and kept in registers (compile-time indices only) until the Jacobian pair loop, which
+    // then neither recomputes u nor calls an exponential.  The primal lane (row i = 4 t + (lane >> 4), unit h = lane & 15) holds
+    // sg[t][j]; the Jacobian lane (i, k) contracts over h, so the values change lanes through LDS right before use (jac_pairs_cached).
+    // NS = 4 m + 1: m full trips of the primal pass; the last particle's partners are split over the four rows of lanes (row r takes
+    // j = 4 r .. 4 r + 3: sgl[]), which would otherwise idle on that trip.  The Jacobian pass runs in m chunks of 4 NS pairs -- the
+    // 4 (NS - 1) off-diagonal pairs of the 4 rows of primal trip c plus the 4 pairs of the last row held by lane row c -- so every lane
+    // of a chunk's hand-off stores registers with compile-time indices.
+    template <int NS> struct PairCache {
+        static constexpr int NC = NS / 4;                         // full trips of the primal pass = chunks of the Jacobian pass
+        static constexpr int SL = 4 * NS;                         // pairs (LDS slots per unit) of one chunk
+        double sg[NS > 0 ? NC : 1][NS > 0 ? NS : 1];
+        double sgl[4];
+    };
+    static constexpr bool pair_cache_ok(int ns, int nthr) { return HS == 16 && HT == 16 && nthr == 64 && ns >= 5 && ns <= 16 && ns % 4 == 1; }
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef double d4_t __attribute__((ext_vector_type(4)));
     static __device__ __forceinline__ d4_t mfma(double a, double bb, d4_t c) {
@@ -151,22 +166,29 @@ struct CgFast {
 #pragma unroll
         for (int f = 0; f < P; ++f) w.tw[1 + f] = th[o_t0w + f * HT + col];
     }
+    // PART 0: every layer's fragments; 1 / 2 / 3: those of layer 0 / the last layer / the final projection only (primal_dense_mfma<true>)
+    template <int PART = 0>
     static __device__ __forceinline__ void load_dense_p(const double* __restrict__ th_in, DenseP& w) {
         const double* th = th_in;
         asm volatile("" : "+s"(th));      // opaque to LICM: keep these loads inside the evaluation, not hoisted + spilled
         const int l = threadIdx.x & 63, col = l & 15, kq = l >> 4;
+        if constexpr (PART == 0 || PART == 1) {
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) { const int f = 4 * ks + kq; w.w0[ks] = f < P ? th[o_W0 + f * HS + col] : 0.0; }
-        w.b0 = th[o_s0b + col]; w.b2 = th[o_s1b + col];
+            for (int ks = 0; ks < 2; ++ks) { const int f = 4 * ks + kq; w.w0[ks] = f < P ? th[o_W0 + f * HS + col] : 0.0; }
+            w.b0 = th[o_s0b + col];
+        }
+        if constexpr (PART == 0 || PART == 2) w.b2 = th[o_s1b + col];
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             const int k = 4 * ks + kq;
-            w.wacb[ks] = th[o_Wa + k * HS + col];
-            w.wacb[4 + ks] = th[o_Wc + k * HS + col];
-            w.wacb[8 + ks] = th[o_Wb + k * HS + col];
-            w.wf[ks] = col < D ? th[o_fw + k * D + col] : 0.0;
+            if constexpr (PART == 0 || PART == 2) {
+                w.wacb[ks] = th[o_Wa + k * HS + col];
+                w.wacb[4 + ks] = th[o_Wc + k * HS + col];
+                w.wacb[8 + ks] = th[o_Wb + k * HS + col];
+            }
+            if constexpr (PART == 0 || PART == 3) w.wf[ks] = col < D ? th[o_fw + k * D + col] : 0.0;
         }
-        w.bf = col < D ? th[o_fb + col] : 0.0;
+        if constexpr (PART == 0 || PART == 3) w.bf = col < D ? th[o_fb + col] : 0.0;
     }
     static __device__ __forceinline__ void load_dense_j(const double* __restrict__ th_in, DenseJ& w) {
         const double* th = th_in;
@@ -345,6 +367,120 @@ struct CgFast {
         }
         asm volatile("" ::: "memory");
     }
+    // primal_pairs_lds of the single-wave sampler at n = NS: the same arithmetic in the same order (m0, m1 are bitwise those of the
+    // generic pass), trips and partners unrolled so that sigmoid(u) of every (pair, unit) lands in a register of the pair cache.
+    template <int NS>
+    static __device__ __forceinline__ void primal_pairs_cached(const CgBlk& b, const WFrag& wfr, double* lds, const CgFastLds& o, PairCache<NS>& pc) {
+        static_assert(NS <= 16 && NS % 4 == 1 && PFWAVE + 64 * 3 <= NS * D * NS * D, "one block of partners, last row split 4 ways, scratch inside J");
+        constexpr int n = NS;
+        WFrag w; load_pair_cols(wfr.th, w);
+        const double *sh = lds + o.sh, *ch = lds + o.ch;
+        double *m0 = lds + o.m0, *m1 = lds + o.m1;
+        const double rn = 1.0 / (double)n;
+        const int lane = b.tid & 63, h = lane & 15, rr = lane >> 4;
+        double* scr = lds + o.J;
+        double* cs = scr + 4 * PFROW;                      // C[a] at cs[a], S[a] at cs[D + a]
+        if (lane < 2 * D) {
+            const int a = lane < D ? lane : lane - D;
+            double acc = 0.0;
+            for (int j = 0; j < n; ++j) {
+                const double sj = sh[j * D + a], cj = ch[j * D + a];
+                acc += lane < D ? 1.0 - 2.0 * (sj * sj) : 2.0 * (sj * cj);
+            }
+            cs[lane] = acc;
+        }
+        const double* row = scr + rr * PFROW;
+        double* slot = scr + rr * PFROW + h * PFS;
+        auto uof = [&](const double* pf) {
+            double u = w.tw[0] + w.tw[1 + 2 * D] * pf[2 * D];
+#pragma unroll
+            for (int a = 0; a < D; ++a) u += w.tw[1 + a] * pf[a] + w.tw[1 + D + a] * pf[D + a];
+            return u;
+        };
+        // the sigmoid is formed HERE: left to itself the compiler sinks it to its use in the Jacobian pass and keeps u, e and 1 + e alive instead
+        auto pin = [](double v) { asm volatile("" : "+v"(v)); return v; };
+#pragma unroll
+        for (int t = 0; t < PairCache<NS>::NC; ++t) {
+            const int i = 4 * t + rr;                  // < n - 1
+            PF6 mine; own_pair(sh, ch, i, h, h < n, mine);
+#pragma unroll
+            for (int a = 0; a < D; ++a) { slot[a] = mine.c2[a]; slot[D + a] = mine.s2[a]; }
+            slot[2 * D] = mine.del;
+            asm volatile("" ::: "memory");             // cross-lane hand-off (LDS executes one wave's accesses in order)
+            double acc = 0.0, rawd = 0.0, pra = 1.0, prb = 1.0;
+#pragma unroll
+            for (int jj = 0; jj + 1 < n; jj += 2) {
+                const double* pa = row + jj * PFS; const double* pb = pa + PFS;
+                const double ua = uof(pa), ub = uof(pb);
+                rawd += pa[2 * D] + pb[2 * D];
+                acc += fmax(ua, 0.0) + fmax(ub, 0.0);
+                const double ea = cg_exp_nonpos(-fabs(ua)), eb = cg_exp_nonpos(-fabs(ub));
+                const double wa = 1.0 + ea, wb = 1.0 + eb;
+                pra *= wa; prb *= wb;
+                pc.sg[t][jj] = pin(sigmoid_from_exp(ua, ea, wa)); pc.sg[t][jj + 1] = pin(sigmoid_from_exp(ub, eb, wb));
+            }
+            if constexpr (n & 1) {
+                const double* pa = row + (n - 1) * PFS;
+                const double ua = uof(pa);
+                rawd += pa[2 * D];
+                acc += fmax(ua, 0.0);
+                const double ea = cg_exp_nonpos(-fabs(ua)), wa = 1.0 + ea;
+                pra *= wa;
+                pc.sg[t][n - 1] = pin(sigmoid_from_exp(ua, ea, wa));
+            }
+            acc += cg_log_ge1(pra * prb);
+            asm volatile("" ::: "memory");             // the next trip's stores stay behind these reads
+            m1[i * HT + h] = acc * rn;
+            if (h < 2 * D) {
+                const int a = h < D ? h : h - D;
+                const double si = sh[i * D + a], ci = ch[i * D + a];
+                const double ct = 1.0 - 2.0 * (si * si), st = 2.0 * (si * ci);
+                m0[i * P + h] = (h < D ? ct * cs[a] + st * cs[D + a] : st * cs[a] - ct * cs[D + a]) * rn;
+            } else if (h == 2 * D) {
+                m0[i * P + h] = rawd * rn;
+            }
+        }
+        {   // last particle: every row of lanes holds its features; row rr sums the partners j = 4 rr .. 4 rr + 3, the partial sums and
+            // products are combined by row 0 in the fixed order of the rows (differs from the one-row order by rounding only)
+            constexpr int i = n - 1;
+            PF6 mine; own_pair(sh, ch, i, h, h < n, mine);
+#pragma unroll
+            for (int a = 0; a < D; ++a) { slot[a] = mine.c2[a]; slot[D + a] = mine.s2[a]; }
+            slot[2 * D] = mine.del;
+            asm volatile("" ::: "memory");
+            double acc = 0.0, rawd = 0.0, pr = 1.0;
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) {
+                const bool ok = 4 * rr + jj < n;       // (row NC: j = n - 1 only; the slots behind it hold finite fill values)
+                const double* pa = row + (4 * rr + jj) * PFS;
+                const double ua = uof(pa);
+                const double ea = cg_exp_nonpos(-fabs(ua)), wa = 1.0 + ea;
+                rawd += ok ? pa[2 * D] : 0.0;
+                acc += ok ? fmax(ua, 0.0) : 0.0;
+                pr *= ok ? wa : 1.0;
+                pc.sgl[jj] = pin(sigmoid_from_exp(ua, ea, wa));
+            }
+            double* part = scr + PFWAVE + lane * 3;    // behind the feature scratch, inside J's slot (lrow_fits)
+            part[0] = acc; part[1] = pr; part[2] = rawd;
+            asm volatile("" ::: "memory");
+            if (rr == 0) {
+                const double* q0 = scr + PFWAVE + h * 3;
+                double sa = q0[0], sp = q0[1], sr = q0[2];
+#pragma unroll
+                for (int r = 1; r < 4; ++r) { sa += q0[r * 48]; sp *= q0[r * 48 + 1]; sr += q0[r * 48 + 2]; }
+                m1[i * HT + h] = (sa + cg_log_ge1(sp)) * rn;
+                if (h < 2 * D) {
+                    const int a = h < D ? h : h - D;
+                    const double si = sh[i * D + a], ci = ch[i * D + a];
+                    const double ct = 1.0 - 2.0 * (si * si), st = 2.0 * (si * ci);
+                    m0[i * P + h] = (h < D ? ct * cs[a] + st * cs[D + a] : st * cs[a] - ct * cs[D + a]) * rn;
+                } else if (h == 2 * D) {
+                    m0[i * P + h] = sr * rn;
+                }
+            }
+        }
+        asm volatile("" ::: "memory");
+    }
     // G pass on the matrix cores.  With the pair-feature matrices (zero diagonal, b = direction)
     //     C_b[k][l] = cos(2 pi r_kl,b / L),   S_b[k][l] = sin(2 pi r_kl,b / L),   R_b[k][l] = S_b[k][l] / |sin(pi r_kl / L)|
     // the sum over l of  sg1_k (odd + evn) - sg1_l (evn - odd)  (see the scalar G pass in jacobian()) becomes
@@ -355,6 +491,11 @@ struct CgFast {
     // A operand: lane (row k = l & 15, l' = 4 ks + (l >> 4)) computes the features of ITS pair once -- no 16-fold
     // redundancy and no DPP broadcast; the pass costs ~4 pair-feature evaluations per lane and tile instead of
     // n/4 x 13 x ~30 VALU instructions.
+    // FOLD (sampler with the pair cache, where registers are scarce): the column factors go into the B operands, so that the six
+    // accumulators per direction collapse into two,  n^2 G_k[h][b] = sg1_k[h] A_b[k][h] + Q_b[k][h]  with
+    //     A_b = sum_l' (c1 W0s C_b - c1 W0c S_b + c2c W0d R_b)[k][l'],   Q_b = sum_l' (-c1 W0s C_b - c1 W0c S_b + c2c W0d R_b)[k][l'] sg1_l'[h]
+    // -- the same products, 64 accumulator registers fewer, G equal up to the order of the sums.
+    template <bool FOLD = false>
     static __device__ __forceinline__ void g_pass_mfma(const CgBlk& b, const WFrag& wfr, int n, double L, double* lds, const CgFastLds& o) {
         const double* th = wfr.th;
         asm volatile("" : "+s"(th));      // opaque to LICM (see load_dense_p)
@@ -369,6 +510,42 @@ struct CgFast {
 #pragma unroll
         for (int a = 0; a < D; ++a) { kc[a] = -c1 * th[o_W0 + a * HS + col]; ksn[a] = c1 * th[o_W0 + (D + a) * HS + col]; }
         const double kd = c2c * th[o_W0 + 2 * D * HS + col];
+        if constexpr (FOLD) {
+            for (int kt = wave; kt < tiles; kt += nw) {
+                const int k = 16 * kt + col;                          // A row of this lane
+                d4_t aA[D], aQ[D];
+#pragma unroll
+                for (int a = 0; a < D; ++a) { aA[a] = d4_t{0, 0, 0, 0}; aQ[a] = aA[a]; }
+                for (int lt = 0; lt < tiles; ++lt) {
+#pragma unroll
+                    for (int ks = 0; ks < 4; ++ks) {
+                        const int lp = 16 * lt + 4 * ks + kq;
+                        const bool inr = lp < n;
+                        PF6 pf; own_pair(sh, ch, k, lp, k < n && inr, pf);
+                        const double bS = inr ? sg1[lp * HS + col] : 0.0;
+                        const double bO = inr ? 1.0 : 0.0;
+#pragma unroll
+                        for (int a = 0; a < D; ++a) {
+                            const double xC = (lp == k) ? 0.0 : pf.c2[a];
+                            const double xS = pf.s2[a], xR = pf.s2[a] * pf.rdel;
+                            aA[a] = mfma(xC, bO * ksn[a], aA[a]); aQ[a] = mfma(xC, -(bS * ksn[a]), aQ[a]);
+                            aA[a] = mfma(xS, bO * kc[a], aA[a]);  aQ[a] = mfma(xS, bS * kc[a], aQ[a]);
+                            aA[a] = mfma(xR, bO * kd, aA[a]);     aQ[a] = mfma(xR, bS * kd, aQ[a]);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int kk = 16 * kt + kq + 4 * r;
+                    if (kk < n) {
+                        const double sgk = sg1[kk * HS + col];
+#pragma unroll
+                        for (int a = 0; a < D; ++a) G[iG(kk, col, a)] = fma(sgk, aA[a][r], aQ[a][r]) * rn * rn;
+                    }
+                }
+            }
+            return;
+        }
         for (int kt = wave; kt < tiles; kt += nw) {
             const int k = 16 * kt + col;                              // A row of this lane
             d4_t pC[D], pS[D], pR[D], sC[D], sS[D], sR[D];            // products with sg1 / row sums
@@ -410,9 +587,11 @@ struct CgFast {
         }
     }
     // dense part of primal(): needs m0, m1 in LDS; fills s1 sg1 sg2 s2 z.  Executed by wave 0; others wait.
+    // LAZY (sampler with the pair cache, where registers are scarce): each layer's weight fragments are loaded right before that layer
+    template <bool LAZY = false>
     static __device__ __forceinline__ void primal_dense_mfma(const CgBlk& b, const WFrag& wfr, const double* x, int n,
                                                              double* lds, const CgFastLds& o) {
-        DenseP w; load_dense_p(wfr.th, w);
+        DenseP w; load_dense_p<LAZY ? 1 : 0>(wfr.th, w);
         double *m0 = lds + o.m0, *s1 = lds + o.s1, *sg1 = lds + o.sg1, *m1 = lds + o.m1, *gbar = lds + o.gbar,
                *sg2 = lds + o.sg2, *s2 = lds + o.s2, *z = lds + o.z;
         const int l = b.tid & 63, col = l & 15, kq = l >> 4;
@@ -443,6 +622,7 @@ struct CgFast {
         }
         b.sync();
         // last layer: u2 = s1 Wa + m1 Wc + gbar Wb + b2;  s2 = s1 + softplus(u2)
+        if constexpr (LAZY) load_dense_p<2>(wfr.th, w);
         for (int t = wave; t < tiles; t += nw) {
             const int ia = 16 * t + col;
             d4_t c = {w.b2, w.b2, w.b2, w.b2};
@@ -464,6 +644,7 @@ struct CgFast {
         }
         b.sync();
         // z = x + s2 Wf + bf
+        if constexpr (LAZY) load_dense_p<3>(wfr.th, w);
         for (int t = wave; t < tiles; t += nw) {
             const int ia = 16 * t + col;
             d4_t c;
@@ -586,10 +767,98 @@ struct CgFast {
         for (int e = b.tid; e < HS * D; e += b.nthr) wfl[e] = th[o_fw + e];
         b.sync();
     }
+    // Pair part of one off-diagonal block, item (i, k), serial over the units h:  J_ik -= U'_i T_ik + V_i diag(sig_t(u_ik)) Wt^T T_ik.
+    // sgof(h, u) returns sigmoid(u_ik[h]); UNR: unroll factor of the unit loop.
+    template <int UNR, class SG>
+    static __device__ __forceinline__ void jac_pair_block(const double* sh, const double* ch, const double* wt, const double* V, const double* Up,
+                                                          double* J, int N, double c1, double c2c, int i, int k, SG&& sgof) {
+        PF6 pf; own_pair(sh, ch, i, k, true, pf);
+        const double rdel = pf.rdel;
+        double tc[D], ts[D], td[D];
+#pragma unroll
+        for (int bb = 0; bb < D; ++bb) { tc[bb] = -c1 * pf.s2[bb]; ts[bb] = c1 * pf.c2[bb]; td[bb] = c2c * (pf.s2[bb] * rdel); }
+        double Jb[D][D];
+#pragma unroll
+        for (int a = 0; a < D; ++a)
+#pragma unroll
+            for (int bb = 0; bb < D; ++bb)
+                Jb[a][bb] = J[(i * D + a) * N + k * D + bb]
+                            - (Up[(i * D + a) * P + bb] * tc[bb] + Up[(i * D + a) * P + D + bb] * ts[bb] + Up[(i * D + a) * P + 2 * D] * td[bb]);
+#pragma unroll UNR
+        for (int h = 0; h < HT; ++h) {
+            const double* wh = wt + h * (P + 1);
+            const double wd = wh[1 + 2 * D];
+            double u = wh[0] + wd * pf.del;
+            double q[D];
+#pragma unroll
+            for (int a = 0; a < D; ++a) {
+                const double wc = wh[1 + a], ws = wh[1 + D + a];
+                u += wc * pf.c2[a] + ws * pf.s2[a];
+                q[a] = wc * tc[a] + ws * ts[a] + wd * td[a];
+            }
+            const double sg = sgof(h, u);
+#pragma unroll
+            for (int a = 0; a < D; ++a) {
+                const double vs = V[iV(i, a, h)] * sg;
+#pragma unroll
+                for (int bb = 0; bb < D; ++bb) Jb[a][bb] -= vs * q[bb];
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < D; ++a)
+#pragma unroll
+            for (int bb = 0; bb < D; ++bb) J[(i * D + a) * N + k * D + bb] = Jb[a][bb];
+    }
+    // Jacobian pair loop of the single-wave sampler at n = NS, sigmoids from the pair cache.  Per chunk c the wave first hands its cached
+    // values over in [unit][slot] order (slot = pair of the chunk), then lane = slot reads its 16 units back and runs the unit loop of
+    // jac_pair_block: same summation order over h as the generic loop.  The hand-off buffer is 16 x 4 NS doubles in slots of the sampler
+    // layout that are dead by now and rewritten by the next evaluation's primal pass before they are read again: sg1 and sg2 (16 NS
+    // doubles each: units 0-3 and 4-7; last read by jac_up_mfma / jac_factors_mfma<1>) and G (units 8-15; last read by jac_bg_mfma).
+    //   slot (NS - 1) r + kk, r < 4, kk < NS - 1:  pair (i = 4 c + r, k = kk + (kk >= i))
+    //   slot 4 (NS - 1) + jj, jj < 4            :  pair (i = NS - 1, k = 4 c + jj)
+    template <int NS>
+    static __device__ __forceinline__ void jac_pairs_cached(const CgBlk& b, double L, double* lds, const CgFastLds& o, const double* wt, double* J,
+                                                            const PairCache<NS>& pc) {
+        constexpr int n = NS, N = n * D, M = NS - 1, SL = PairCache<NS>::SL, NC = PairCache<NS>::NC;
+        static_assert(NS % 4 == 1 && SL <= 64 && 4 * SL <= NS * HS && 8 * SL <= NS * SPG, "chunking / hand-off buffer of the pair cache");
+        const double *sh = lds + o.sh, *ch = lds + o.ch, *V = lds + o.V, *Up = lds + o.Up;
+        const double c1 = 2.0 * CG_PI / L, c2c = CG_PI / (2.0 * L);
+        const int lane = b.tid & 63, h = lane & 15, rr = lane >> 4;
+        auto unit_row = [&](int hh) { return hh < 4 ? o.sg1 + hh * SL : hh < 8 ? o.sg2 + (hh - 4) * SL : o.G + (hh - 8) * SL; };
+        double* bw = lds + unit_row(h) + rr * M;            // hand-off: this lane's unit, first slot of its particle row
+        double* bl = lds + unit_row(h) + 4 * M;             // ... first slot of the last particle's pairs
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            asm volatile("" ::: "memory");             // the stores stay behind the previous chunk's reads
+            const int i0 = 4 * c + rr;                 // (the diagonal pair j = i0 has no slot)
+#pragma unroll
+            for (int j = 0; j < n; ++j) {
+                if (j < 4 * c) bw[j] = pc.sg[c][j];
+                else if (j > 4 * c + 3) bw[j - 1] = pc.sg[c][j];
+                else if (j != i0) bw[j - (j > i0 ? 1 : 0)] = pc.sg[c][j];
+            }
+            if (rr == c) {                             // the last particle's pairs with k = 4 c .. 4 c + 3 are held by lane row c
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) bl[jj] = pc.sgl[jj];
+            }
+            asm volatile("" ::: "memory");             // cross-lane hand-off (LDS executes one wave's accesses in order)
+            if (lane < SL) {
+                const int r = lane / M, kk = lane - r * M;
+                const bool last = lane >= 4 * M;
+                const int i = last ? NS - 1 : 4 * c + r;
+                const int k = last ? 4 * c + (lane - 4 * M) : kk + (kk >= i ? 1 : 0);
+                const double* br = lds + lane;
+                jac_pair_block<4>(sh, ch, wt, V, Up, J, N, c1, c2c, i, k, [&](int hh, double) { return br[unit_row(hh)]; });
+            }
+        }
+        asm volatile("" ::: "memory");
+    }
     // The whole Jacobian assembly on the MFMA / DPP path (double, spsize = tpsize = 16).  Order chosen so that
     // V can reuse Bm's LDS slot:  U,Bm | G  ->  Up  ->  J = Bm G  ->  V  ->  J += pair part  ->  diagonal blocks.
+    // NS > 0 (single-wave sampler specialised on n = NS): the pair part takes its sigmoids from the pair cache.
+    template <int NS = 0>
     static __device__ __forceinline__ void jacobian_mfma(const CgBlk& b, const double* __restrict__ th, const WFrag& w, int n,
-                                                         double L, double* lds, const CgFastLds& o) {
+                                                         double L, double* lds, const CgFastLds& o, const PairCache<NS>* pc = nullptr) {
         const double *sh = lds + o.sh, *ch = lds + o.ch;
         double *V = lds + o.V, *Up = lds + o.Up, *J = w.Jext ? w.Jext : lds + o.J;
         const int N = n * D;
@@ -602,7 +871,7 @@ struct CgFast {
         jac_factors_mfma<0>(b, w, n, lds, o, wfl);
 #endif
         CG_STAMP(5)
-        g_pass_mfma(b, w, n, L, lds, o);
+        g_pass_mfma<(NS > 0)>(b, w, n, L, lds, o);
         b.sync();
         CG_STAMP(6)
 #if !defined(CG_EXP_NO_DENSE)
@@ -616,51 +885,17 @@ struct CgFast {
 #endif
         b.sync();
         CG_STAMP(9)
-        for (int e = b.tid; e < n * n; e += b.nthr) {
-            const int i = e / n, k = e - i * n;
-            if (i == k) continue;
-            PF6 pf; own_pair(sh, ch, i, k, true, pf);
-            const double rdel = pf.rdel;
-            double tc[D], ts[D], td[D];
-#pragma unroll
-            for (int bb = 0; bb < D; ++bb) { tc[bb] = -c1 * pf.s2[bb]; ts[bb] = c1 * pf.c2[bb]; td[bb] = c2c * (pf.s2[bb] * rdel); }
-            double Jb[D][D];
-#pragma unroll
-            for (int a = 0; a < D; ++a)
-#pragma unroll
-                for (int bb = 0; bb < D; ++bb)
-                    Jb[a][bb] = J[(i * D + a) * N + k * D + bb]
-                                - (Up[(i * D + a) * P + bb] * tc[bb] + Up[(i * D + a) * P + D + bb] * ts[bb] + Up[(i * D + a) * P + 2 * D] * td[bb]);
-#pragma unroll 4
-            for (int h = 0; h < HT; ++h) {
-                const double* wh = wt + h * (P + 1);
-                const double wd = wh[1 + 2 * D];
-                double u = wh[0] + wd * pf.del;
-                double q[D];
-#pragma unroll
-                for (int a = 0; a < D; ++a) {
-                    const double wc = wh[1 + a], ws = wh[1 + D + a];
-                    u += wc * pf.c2[a] + ws * pf.s2[a];
-                    q[a] = wc * tc[a] + ws * ts[a] + wd * td[a];
-                }
-#if defined(CG_EXP_FREE_SIGMA)      /* timing experiment (garbage numbers): what a CACHED sigmoid would cost -- an upper bound on what sharing
-                                       the exponential of the primal pass with this pass can gain (profiles/r03*_experiments.txt) */
-                const double sg = 0.25 + 1e-3 * u;
-#else
-                const double sg = sigmoid_only(u);
-#endif
-#pragma unroll
-                for (int a = 0; a < D; ++a) {
-                    const double vs = V[iV(i, a, h)] * sg;
-#pragma unroll
-                    for (int bb = 0; bb < D; ++bb) Jb[a][bb] -= vs * q[bb];
-                }
+#if !defined(CG_EXP_FREE_JPAIRS)    /* timing experiment (garbage numbers): the Jacobian pair loop free -- the bound on any further work on it */
+        if constexpr (NS > 0) {
+            jac_pairs_cached<NS>(b, L, lds, o, wt, J, *pc);
+        } else {
+            for (int e = b.tid; e < n * n; e += b.nthr) {
+                const int i = e / n, k = e - i * n;
+                if (i == k) continue;
+                jac_pair_block<4>(sh, ch, wt, V, Up, J, N, c1, c2c, i, k, [](int, double u) { return sigmoid_only(u); });
             }
-#pragma unroll
-            for (int a = 0; a < D; ++a)
-#pragma unroll
-                for (int bb = 0; bb < D; ++bb) J[(i * D + a) * N + k * D + bb] = Jb[a][bb];
         }
+#endif
         b.sync();
         CG_STAMP(10)
         if (w.Jext) {
@@ -816,9 +1051,10 @@ struct CgFast {
 #else       // host builds: declarations only, so that the `if constexpr (CG_ON_DEVICE && ...)` branches of primal() / jacobian() parse
     static bool primal_pairs_lds_fits(const CgBlk&, int);
     static void primal_pairs_lds(const CgBlk&, const WFrag&, int, double*, const CgFastLds&);
+    template <int NS> static void primal_pairs_cached(const CgBlk&, const WFrag&, double*, const CgFastLds&, PairCache<NS>&);
     static void primal_pairs_dpp(const CgBlk&, const WFrag&, int, double*, const CgFastLds&);
-    static void primal_dense_mfma(const CgBlk&, const WFrag&, const double*, int, double*, const CgFastLds&);
-    static void jacobian_mfma(const CgBlk&, const double*, const WFrag&, int, double, double*, const CgFastLds&);
+    template <bool LAZY = false> static void primal_dense_mfma(const CgBlk&, const WFrag&, const double*, int, double*, const CgFastLds&);
+    template <int NS = 0> static void jacobian_mfma(const CgBlk&, const double*, const WFrag&, int, double, double*, const CgFastLds&, const PairCache<NS>* = nullptr);
     static void primal_pairs_jet_dpp(const CgBlk&, const double*, int, Jet2*, const CgFastLds&);
     static void g_pass_jet_dpp(const CgBlk&, const double*, int, double, Jet2*, const CgFastLds&);
 #endif
@@ -826,10 +1062,11 @@ struct CgFast {
     // ---------------------------------------------------------------------------------------
     // primal pass: fills sh,ch,m0,s1,sg1,m1,gbar,cb,sg2,s2,z in LDS.
     // ---------------------------------------------------------------------------------------
-    template <class T>
+    template <class T, int NS = 0>
     // hot >= 0 (jet types only): the particle whose coordinate carries the tangent of this directional pass.
+    // NS > 0 (single-wave sampler specialised on n = NS, MFMA / DPP path): the pair pass also fills the pair cache *pc.
     static CG_DEVI void primal(const CgBlk& b, const double* __restrict__ th, const T* x /*n*D*/,
-                               int n, double L, T* lds, const CgFastLds& o, const WFrag* wf = nullptr, int hot = -1) {
+                               int n, double L, T* lds, const CgFastLds& o, const WFrag* wf = nullptr, int hot = -1, PairCache<NS>* pc = nullptr) {
         T *sh = lds + o.sh, *ch = lds + o.ch, *m0 = lds + o.m0, *s1 = lds + o.s1, *sg1 = lds + o.sg1,
                *m1 = lds + o.m1, *gbar = lds + o.gbar, *cb = lds + o.cb, *sg2 = lds + o.sg2, *s2 = lds + o.s2,
                *z = lds + o.z;
@@ -843,7 +1080,8 @@ struct CgFast {
         bool pairs_done = false;
         if constexpr (CG_ON_DEVICE && sizeof(T) == sizeof(double) && HS == 16 && HT == 16) {
             if (wf) {
-                if (primal_pairs_lds_fits(b, n)) primal_pairs_lds(b, *wf, n, (double*)lds, o);
+                if constexpr (NS > 0) primal_pairs_cached<NS>(b, *wf, (double*)lds, o, *pc);
+                else if (primal_pairs_lds_fits(b, n)) primal_pairs_lds(b, *wf, n, (double*)lds, o);
                 else primal_pairs_dpp(b, *wf, n, (double*)lds, o);
                 pairs_done = true;
             }
@@ -957,7 +1195,7 @@ struct CgFast {
 #if defined(CG_EXP_NO_DENSE)
             if (wf) { for (int e = b.tid; e < n * D; e += b.nthr) z[e] = x[e] + 1e-3 * m1[e]; b.sync(); CG_STAMP(3) return; }
 #endif
-            if (wf) { primal_dense_mfma(b, *wf, (const double*)x, n, (double*)lds, o); CG_STAMP(3) return; }
+            if (wf) { primal_dense_mfma<(NS > 0)>(b, *wf, (const double*)x, n, (double*)lds, o); CG_STAMP(3) return; }
         }
         // layer 0 of the one-particle stream: u1_i = W0^T m0_i + b0 (s0 = 0, src/flow.py:16-18,45)
         for (int e = b.tid; e < n * HS; e += b.nthr) {
@@ -1008,16 +1246,16 @@ struct CgFast {
     // ---------------------------------------------------------------------------------------
     // Jacobian assembly (needs primal() results in LDS).  Writes J (N x N, N = n*D, row-major).
     // ---------------------------------------------------------------------------------------
-    template <class T>
+    template <class T, int NS = 0>
     static CG_DEVI void jacobian(const CgBlk& b, const double* __restrict__ th, int n, double L,
-                                 T* lds, const CgFastLds& o, const WFrag* wf = nullptr) {
+                                 T* lds, const CgFastLds& o, const WFrag* wf = nullptr, const PairCache<NS>* pc = nullptr) {
         const T *sh = lds + o.sh, *ch = lds + o.ch, *sg1 = lds + o.sg1, *sg2 = lds + o.sg2;
         T *U = lds + o.U, *V = lds + o.V, *Bm = lds + o.Bm, *Up = lds + o.Up, *G = lds + o.G, *J = lds + o.J;
         const int N = n * D;
         const double rn = 1.0 / (double)n;
         const double c1 = 2.0 * CG_PI / L, c2c = CG_PI / (2.0 * L);
         if constexpr (CG_ON_DEVICE && sizeof(T) == sizeof(double) && HS == 16 && HT == 16) {
-            if (wf) { jacobian_mfma(b, th, *wf, n, L, (double*)lds, o); return; }
+            if (wf) { jacobian_mfma<NS>(b, th, *wf, n, L, (double*)lds, o, pc); return; }
         }
         // two-particle layer weights -> arena, [h][bias, w_0..w_{P-1}]: the Jacobian pass reads them with broadcast loads
         double* wt = (double*)(lds + o.wt);
@@ -1172,12 +1410,15 @@ struct CgFast {
 
     // log Psi(x) = log phi(z(x)) + 1/2 log|det J|  ->  out = [Re, Im]  (src/logpsi.py:30-31)
     // also returns the two pieces separately (make_logphi_logjacdet, src/logpsi.py:35-53).
+    // NS > 0: n = NS, one wave, wf given (pair_cache_ok): the pair passes share their exponentials through a PairCache.
+    template <int NS = 0>
     static CG_DEVI void logpsi(const CgBlk& b, const double* __restrict__ th, const double* x /*LDS*/,
                                const double* __restrict__ spk, const int* __restrict__ sidx, int n, double L,
                                double* lds, const CgFastLds& o, double& re_phi, double& im_phi, double& half_logdetJ,
                                const WFrag* wf = nullptr) {
-        primal(b, th, x, n, L, lds, o, wf);
-        jacobian(b, th, n, L, lds, o, wf);
+        PairCache<NS> pc;
+        primal(b, th, x, n, L, lds, o, wf, -1, &pc);
+        jacobian(b, th, n, L, lds, o, wf, (const PairCache<NS>*)&pc);
         int* perm = (int*)(lds + o.perm);
         double la, ar;
 #if defined(__HIP_DEVICE_COMPILE__)

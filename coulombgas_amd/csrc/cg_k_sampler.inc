@@ -99,7 +99,8 @@ __global__ void __launch_bounds__(MAXT, (MAXT <= 256 ? CG_WAVES_PER_EU : 1)) k_m
 #else
             const CgBlk& be = b;
 #endif
-            F::logpsi(be, theta, xp, kv, nullptr, n, m.L, lds, lay, re, im, h, wf);        // (no index table: kv[j] is k_{sidx[j]})
+            // (no index table: kv[j] is k_{sidx[j]}; specialised single-wave workgroups: the pair passes share their exponentials)
+            F::template logpsi<F::pair_cache_ok(NS, MAXT) ? NS : 0>(be, theta, xp, kv, nullptr, n, m.L, lds, lay, re, im, h, wf);
             const double lp = 2.0 * (re + h);
             if (b.tid == 0) {
                 int acc = 1;
