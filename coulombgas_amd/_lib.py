@@ -57,6 +57,9 @@ PROTOTYPES = {
     "cg_mcmc_accept_rate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_double)]),
     "cg_wrap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "cg_ewald": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "cg_set_structure": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double]),
+    "cg_structure_size": (C.c_int, [C.c_void_p]),
+    "cg_structure_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "cg_grad_laplacian": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cg_param_vjp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cg_quantum_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),

@@ -24,6 +24,10 @@ class NullComm:
         """in-place mean over the ranks of a device-resident array (or of `count` elements from `index`): nothing to do"""
         return a
 
+    def psum_d(self, a, count=None, index=0):
+        """in-place sum over the ranks of a device-resident array (or of `count` elements from `index`): nothing to do"""
+        return a
+
     def accept_rate(self, engine, denom):
         """accepted moves of the engine's last chain / denom (src/MCMC.py:37-39)"""
         return engine.mcmc_accepts() / float(denom) if denom else 0.0
@@ -89,13 +93,22 @@ class RcclComm:
     def pmean_d(self, a, count=None, index=0):
         """in-place RCCL all-reduce (mean) of a DeviceArray, or of `count` doubles from element `index` of its buffer, on the
         engine's stream: no host staging (main.py:280, src/VMC.py:46-53, src/sr.py:73-82)"""
-        from ._lib import lib, check
+        from ._lib import lib
+        return self._reduce_d(a, count, index, lib().cg_allreduce_mean, "pmean_d")
+
+    def psum_d(self, a, count=None, index=0):
+        """the same with a SUM (cg_allreduce_sum): packed sums that carry their own count, e.g. the structure observables"""
+        from ._lib import lib
+        return self._reduce_d(a, count, index, lib().cg_allreduce_sum, "psum_d")
+
+    def _reduce_d(self, a, count, index, fn, name):
+        from ._lib import check
         base = a.base                                        # a DeviceArray is its own base (index 0); a DeviceView a window
         total = base.size * (2 if base.complex_pairs else 1) - a.index        # doubles from a's first element to the buffer's end
         n = (a.size * (2 if a.complex_pairs else 1) - index) if count is None else count
         if index < 0 or n < 0 or index + n > total:
-            raise IndexError("pmean_d: [%d, %d) outside a device buffer of %d doubles" % (index, index + n, total))
-        check(lib().cg_allreduce_mean(self._h, a.ptr_at(index), int(n)), self.engine._ctx)
+            raise IndexError("%s: [%d, %d) outside a device buffer of %d doubles" % (name, index, index + n, total))
+        check(fn(self._h, a.ptr_at(index), int(n)), self.engine._ctx)
         a.version += 1
         return a
 

@@ -2,6 +2,7 @@
 // solver of libcoulombgas_hip.so (C-ABI: include/coulombgas.h).  The walker kernels live in cg_k_*.hip.
 #include "cg_host.hpp"
 #include "cg_ewald.hpp"
+#include "cg_structure.hpp"
 #include "cg_rng.hpp"
 
 thread_local std::string g_last_error;
@@ -22,6 +23,57 @@ __global__ void k_ewald(const double* __restrict__ x, int B, int n, double L, do
         if (b.tid == 0) V[w] = v;
         b.sync();
     }
+}
+
+// Structure observables (cg_structure.hpp): |rho_k|^2, rho_k and the pair histogram of every walker, summed over the rows of the batch.
+// grid (x: workgroups along the rows, y: slices of CG_STRUCT_KPT * 256 k vectors; slice 0 also takes the histogram); a workgroup
+// walks its rows one after the other and writes one row of partial sums each; k_structure_reduce sums the rows in fixed order.
+template <int D>
+__global__ void __launch_bounds__(256) k_structure(const double* __restrict__ x, int B, int rows, int n, double L,
+                                                   const int* __restrict__ K, int nK, int Kmax, int nbins, double scale,
+                                                   double* __restrict__ partial) {
+    extern __shared__ double lds[];
+    const CgBlk b{(int)threadIdx.x, (int)blockDim.x};
+    const int N = n * D, T = Kmax + 1, W = 3 * nK + nbins + 1;
+    double* xs = lds;
+    double* tab = lds + ((N + 1) & ~1);
+    unsigned* hist = (unsigned*)(tab + (size_t)N * T * 2);
+    const int k0 = blockIdx.y * (CG_STRUCT_KPT * b.nthr);
+    const bool pairs = blockIdx.y == 0;
+    int kv[CG_STRUCT_KPT][D];
+    cg_structure_load_k<D>(b, K, k0, nK, kv);
+    for (int e = b.tid; e <= nbins; e += b.nthr) hist[e] = 0u;
+    CgStructAcc acc;
+    for (int row = blockIdx.x; row < rows; row += gridDim.x) {
+        acc.zero();
+        for (int w = row; w < B; w += rows) {
+            for (int e = b.tid; e < N; e += b.nthr) xs[e] = x[(size_t)w * N + e];
+            b.sync();
+            cg_structure_tables<D>(b, xs, n, L, T, tab);
+            b.sync();
+            cg_structure_add_walker<D>(b, tab, n, T, k0, nK, kv, acc);
+            if (pairs) cg_structure_pairs<D>(b, xs, n, L, nbins, scale, hist);
+            b.sync();
+        }
+        double* out = partial + (size_t)row * W;
+        cg_structure_store_k(b, k0, nK, acc, out);
+        if (pairs) cg_structure_store_hist(b, nbins, hist, out + 3 * nK);
+    }
+}
+// out[p] = the sum of column p over the rows in the order of cg_structure.hpp (64 columns x CG_STRUCT_GROUPS row groups per workgroup);
+// out[W] = the number of walkers
+__global__ void __launch_bounds__(64 * CG_STRUCT_GROUPS) k_structure_reduce(const double* __restrict__ partial, int rows, int W, double count,
+                                                                            double* __restrict__ out) {
+    __shared__ double part[64 * CG_STRUCT_GROUPS];
+    const int c = threadIdx.x & 63, g = threadIdx.x >> 6, p = blockIdx.x * 64 + c;
+    part[threadIdx.x] = p < W ? cg_structure_group_sum(partial, rows, W, p, g) : 0.0;
+    __syncthreads();
+    if (g == 0 && p < W) {
+        double a = part[c];
+        for (int q = 1; q < CG_STRUCT_GROUPS; ++q) a += part[q * 64 + c];
+        out[p] = a;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) out[W] = count;
 }
 
 __global__ void k_wrap(double* __restrict__ x, size_t count, double L) {
@@ -328,6 +380,7 @@ void cg_destroy(cg_ctx* c) {
     if (c->d_tab) (void)hipFree(c->d_tab);
     if (c->d_G) (void)hipFree(c->d_G);
     if (c->d_gk) (void)hipFree(c->d_gk);
+    if (c->d_K) (void)hipFree(c->d_K);
     if (c->d_accept) (void)hipFree(c->d_accept);
     if (c->d_rate) (void)hipFree(c->d_rate);
     if (c->ev_a) (void)hipEventDestroy(c->ev_a);
@@ -501,6 +554,71 @@ int cg_ewald(cg_ctx* c, const double* x, int B, double* V) {
                            c->rs, (const int*)c->d_G, (const double*)c->d_gk, c->nG, c->Gmax, c->g0, (double*)av.dev);
     }
     if ((rc = unstage(c, av))) return rc;
+    return finish(c);
+}
+
+/* ---- structure observables (cg_structure.hpp) ---- */
+int cg_set_structure(cg_ctx* c, const int64_t* K, int nK, int nbins, double rmax) {
+    if (!c || !K || nK < 1 || nK > (1 << 24) || nbins < 1 || nbins > (1 << 24) || !(rmax > 0) || !(rmax <= 0.5))
+        CG_FAIL(c, CG_ERR_ARG, "cg_set_structure: bad argument (nK=%d nbins=%d rmax=%g); 1 <= nK, nbins <= 2^24, 0 < rmax <= 0.5", nK, nbins, rmax);
+    CG_HIP(c, hipSetDevice(c->device));
+    const int D = c->dim;
+    std::vector<int> k32((size_t)nK * D);
+    int kmax = 0;
+    for (size_t e = 0; e < k32.size(); ++e) {
+        const int64_t v = K[e];
+        if (v > 4096 || v < -4096) CG_FAIL(c, CG_ERR_ARG, "cg_set_structure: |k| component %lld too large (<= 4096)", (long long)v);
+        k32[e] = (int)v; kmax = std::max(kmax, (int)std::llabs(v));
+    }
+    const size_t lds = cg_structure_lds_bytes(c->n, D, kmax, nbins);
+    if (lds > 160 * 1024)
+        CG_FAIL(c, CG_ERR_UNSUPPORTED, "cg_set_structure: n=%d dim=%d max|k|=%d nbins=%d needs %zu bytes of LDS per workgroup (> 160 KiB): "
+                "16 n dim (max|k| + 1) bytes of tables + 4 (nbins + 1) of histogram", c->n, D, kmax, nbins, lds);
+    CG_HIP(c, hipStreamSynchronize(c->stream));
+    c->have_structure = false;
+    if (c->d_K) { (void)hipFree(c->d_K); c->d_K = nullptr; }
+    CG_HIP(c, hipMalloc((void**)&c->d_K, sizeof(int) * k32.size()));
+    CG_HIP(c, hipMemcpy(c->d_K, k32.data(), sizeof(int) * k32.size(), hipMemcpyHostToDevice));
+    c->nK = nK; c->Kmax = kmax; c->nbins = nbins; c->rmax = rmax; c->have_structure = true;
+    return CG_OK;
+}
+int cg_structure_size(const cg_ctx* c) {
+    if (!c) return CG_ERR_ARG;
+    if (!c->have_structure) return CG_ERR_STATE;
+    return 3 * c->nK + c->nbins + 2;
+}
+int cg_structure_sums(cg_ctx* c, const double* x, int B, double* out) {
+    if (!c || B < 0) return CG_ERR_ARG;
+    if (!c->have_structure) CG_FAIL(c, CG_ERR_STATE, "cg_structure_sums: cg_set_structure has not been called");
+    if (!out || (B > 0 && !x)) CG_FAIL(c, CG_ERR_ARG, "cg_structure_sums: NULL argument");
+    CG_HIP(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = arena_reset(c))) CG_FAIL(c, rc, "cg_structure_sums: arena");
+    const int n = c->n, D = c->dim, N = n * D, W = 3 * c->nK + c->nbins + 1, rows = cg_structure_rows(B);
+    Arg ax{B > 0 ? (void*)x : nullptr, nullptr, sizeof(double) * (size_t)B * N, true, false};
+    Arg ao{out, nullptr, sizeof(double) * (size_t)(W + 1), false, true};
+    if ((rc = stage(c, ax)) || (rc = stage(c, ao))) return rc;
+    double* partial = nullptr;
+    if (rows > 0) {
+        partial = (double*)arena_take(c, sizeof(double) * (size_t)rows * W);
+        if (!partial) CG_FAIL(c, CG_ERR_HIP, "cg_structure_sums: workspace allocation failed");
+        const int nt = 256, want = cg_tune::struct_grid();
+        const dim3 grid(want > 0 ? std::min(want, rows) : rows, (c->nK + CG_STRUCT_KPT * nt - 1) / (CG_STRUCT_KPT * nt));
+        const size_t lds = cg_structure_lds_bytes(n, D, c->Kmax, c->nbins);
+        const double scale = (double)c->nbins / c->rmax;
+        if (D == 2) {
+            if ((rc = set_lds(c, k_structure<2>, lds))) return rc;
+            hipLaunchKernelGGL((k_structure<2>), grid, dim3(nt), lds, c->stream, (const double*)ax.dev, B, rows, n, c->L, (const int*)c->d_K,
+                               c->nK, c->Kmax, c->nbins, scale, partial);
+        } else {
+            if ((rc = set_lds(c, k_structure<3>, lds))) return rc;
+            hipLaunchKernelGGL((k_structure<3>), grid, dim3(nt), lds, c->stream, (const double*)ax.dev, B, rows, n, c->L, (const int*)c->d_K,
+                               c->nK, c->Kmax, c->nbins, scale, partial);
+        }
+    }
+    hipLaunchKernelGGL(k_structure_reduce, dim3((W + 63) / 64), dim3(64 * CG_STRUCT_GROUPS), 0, c->stream, (const double*)partial, rows, W, (double)B,
+                       (double*)ao.dev);
+    if ((rc = unstage(c, ao))) return rc;
     return finish(c);
 }
 

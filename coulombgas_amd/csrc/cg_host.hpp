@@ -64,6 +64,11 @@ struct cg_ctx {
     int nG = 0, Gmax = 0;
     int* d_G = nullptr;
     double* d_gk = nullptr;
+    // structure observables (cg_set_structure)
+    bool have_structure = false;
+    int nK = 0, Kmax = 0, nbins = 0;
+    double rmax = 0;
+    int* d_K = nullptr;
     int ptr_mode = CG_PTR_HOST;
     int block_threads = 0;
     int cu_count = 256;
@@ -224,6 +229,8 @@ inline int van_par_waves()           { return cg_env_int("CG_VAN_PAR_WAVES", 0);
 inline int van_grad_reg()            { return cg_env_int("CG_VAN_GRAD_REG", 1); }                    // sequential score kernel: -1 runtime dimensions, 0 compile-time
                                        // dimensions, 1 (> 0) + the gradient row in registers where the workgroup has <= 4 waves, 2 also holds it to <= 4 waves
 inline int van_static(int B, int cu) { return cg_env_int("CG_VAN_STATIC", B <= 16 * cu ? 1 : 0); }   // sampler / log-probability with compile-time model dimensions
+// structure observables (cg_hip.hip)
+inline int struct_grid()             { return cg_env_int("CG_STRUCT_GRID", 0); }                     // workgroups of cg_structure_sums along the rows (0: one per row; same bits at any value)
 // solver (cg_solve.inc)
 inline int fisher_slices()           { return cg_env_int("CG_FISHER_SLICES", 0); }                   // batch slices of cg_fisher_real (0: by occupancy)
 inline int chol_quadrant_blocks()    { return cg_env_int("CG_CHOL_QUADRANT_BLOCKS", 1024); }         // fewer 64 x 64 blocks than this: a wave per quadrant (once per process)

@@ -183,6 +183,21 @@ class Engine:
             check(lib().cg_set_ewald(self._ctx, float(kappa), _p(G), G.shape[0], float(rs)), self._ctx)
             self._ewald = key
 
+    def set_structure(self, K, nbins, rmax):
+        """k vectors (nK, dim) integers, radial bins and their range (units of L) of structure_sums (cg_set_structure)"""
+        K = np.ascontiguousarray(K, dtype=np.int64).reshape(-1, self.dim)
+        key = (K.tobytes(), int(nbins), float(rmax))
+        if getattr(self, "_structure", None) != key:
+            check(lib().cg_set_structure(self._ctx, _p(K), K.shape[0], int(nbins), float(rmax)), self._ctx)
+            self._structure = key
+
+    def structure_size(self):
+        """length of the packed vector of structure_sums: 3 nK + nbins + 2"""
+        size = lib().cg_structure_size(self._ctx)
+        if size < 0:
+            raise _lib.CoulombGasError(size, "cg_structure_size: cg_set_structure has not been called")
+        return int(size)
+
     def device_mode(self, on=True):
         self._mode = _lib.CG_PTR_DEVICE if on else _lib.CG_PTR_HOST
         check(lib().cg_set_pointer_mode(self._ctx, self._mode), self._ctx)
@@ -290,6 +305,13 @@ class Engine:
         V = np.empty(xb.shape[0])
         check(lib().cg_ewald(self._ctx, _p(xb), xb.shape[0], _p(V)), self._ctx)
         return V.reshape(lead)
+
+    def structure_sums(self, x):
+        """packed sums over the batch of |rho_k|^2, rho_k, the pair histogram and the walker count (cg_structure_sums)"""
+        xb, _ = self._xb(x)
+        out = np.empty(self.structure_size())
+        check(lib().cg_structure_sums(self._ctx, _p(xb), xb.shape[0], _p(out)), self._ctx)
+        return out
 
     def grad_laplacian(self, x, state_idx, mode=_lib.CG_LAP_EXACT, v=None):
         xb, lead = self._xb(x)
@@ -491,6 +513,17 @@ class Engine:
         self._dev_call(lib().cg_ewald, x_d.ptr, int(x_d.shape[0]), V.ptr)
         V.version += 1
         return V
+
+    def structure_sums_d(self, x_d, acc=None):
+        """cg_structure_sums of device-resident walkers into the scratch array "structure"; with acc (a DeviceArray of the same
+        size) the sums are added into it on the device and acc is returned"""
+        size = self.structure_size()
+        out = self.scratch("structure", (size,))
+        self._dev_call(lib().cg_structure_sums, x_d.ptr, int(x_d.shape[0]), out.ptr)
+        out.version += 1
+        if acc is None:
+            return out
+        return self.axpby_d(1.0, out, 1.0, acc, count=size)
 
     def local_energy_d(self, grad_d, lap_d, V_d, logp_states_d, Vconst, beta):
         """K8: (E_loc (B) complex, F_loc (B), moments (10)) of src/VMC.py:39-58 before the pmean"""

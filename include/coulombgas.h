@@ -115,6 +115,31 @@ int cg_wrap(cg_ctx* ctx, double* x, int B);
  * src/potential.py:36-77 */
 int cg_ewald(cg_ctx* ctx, const double* x, int B, double* V);
 
+/* ---- structure observables --------------------------------------------------------------- */
+
+/* Static structure factor and pair correlation function of a walker batch, reduced over the batch on the device.  The reference has
+ * no counterpart (it reports the energy and entropy moments of src/VMC.py:44-53 only); conventions as in its Ewald sum
+ * (src/potential.py:47-48).  For each walker x (n,dim), with the ctx's box L:
+ *   rho_k = sum_i exp(2 pi i k.x_i / L) for each of the nK integer vectors k;
+ *   every pair i < j: r~ = (x_i - x_j)/L - rint(.) (nearest image), d = |r~|, t = d * (nbins / rmax), bin (int)t if t < nbins, else the
+ *   overflow bin nbins (a non-finite distance counts as overflow: the pair count is conserved).
+ * K: HOST pointer, nK x dim integers (k = 0 is allowed: |rho_0|^2 = n^2), |component| <= 4096; nbins >= 1; 0 < rmax <= 0.5 (units of
+ * L: every counted shell lies inside the nearest-image cell).  CG_ERR_UNSUPPORTED when the tables of one walker, 16 n dim (max|k| + 1)
+ * bytes, and the histogram do not fit the 160 KiB of LDS of a workgroup. */
+int cg_set_structure(cg_ctx* ctx, const int64_t* K, int nK, int nbins, double rmax);
+/* 3 nK + nbins + 2; CG_ERR_STATE before cg_set_structure */
+int cg_structure_size(const cg_ctx* ctx);
+/* x (B,n,dim), need not be wrapped into the box; out (cg_structure_size) doubles, SUMS over the batch, not means:
+ *   [0, nK)                 sum_b |rho_k|^2
+ *   [nK, 3 nK)              sum_b rho_k as (re, im) pairs
+ *   [3 nK, 3 nK + nbins]    pair counts per bin, the last one the overflow (integers held exactly in doubles)
+ *   [3 nK + nbins + 1]      number of walkers summed (B)
+ * so that cg_axpby(1, out, 1, acc) accumulates over calls, one cg_allreduce_sum reduces over ranks, and the accumulated vector
+ * normalises itself: S(k) = out[k] / (n count), g(r_b) = hist_b L^dim / (count n(n-1)/2 V_b).  Both pointer modes.  B == 0 writes
+ * zeros.  Fixed summation order, no floating-point atomics: two calls on the same input agree bit for bit (csrc/cg_structure.hpp
+ * states the order).  NaN in -> NaN in the rho sums the walker enters, its pairs in the overflow bin; never aborts. */
+int cg_structure_sums(cg_ctx* ctx, const double* x, int B, double* out);
+
 /* ---- local energy ingredients ------------------------------------------------------------ */
 
 /* grad (B,n,dim,2) complex, lap (B,2) complex of log Psi w.r.t. x:
