@@ -19,9 +19,10 @@ from .freefermion import pretrain, exact_free_energy
 from .utils import shard, replicate
 from .engine import Engine
 from .structure import make_structure_observable
+from .momentum import make_momentum_observable
 
 __all__ = ["sp_orbitals", "twist_sort", "FermiNet", "kpoints", "Madelung", "potential_energy", "make_logpsi", "make_logphi_logjacdet",
            "make_logpsi_grad_laplacian", "make_logp", "make_quantum_score", "mcmc",
            "sample_stateindices_and_x", "make_loss", "make_observable", "fisher_sr", "hybrid_fisher_sr", "apply_updates", "train", "make_update", "adam", "GroundStateSampler",
            "ckpt_filename", "load_data", "save_data", "pretrained_model_filename", "Transformer", "make_autoregressive_sampler", "make_classical_score", "pretrain", "exact_free_energy",
-           "shard", "replicate", "Engine", "make_structure_observable"]
+           "shard", "replicate", "Engine", "make_structure_observable", "make_momentum_observable"]

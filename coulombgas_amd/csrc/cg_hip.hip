@@ -3,6 +3,7 @@
 #include "cg_host.hpp"
 #include "cg_ewald.hpp"
 #include "cg_structure.hpp"
+#include "cg_momentum.hpp"
 #include "cg_rng.hpp"
 
 thread_local std::string g_last_error;
@@ -74,6 +75,18 @@ __global__ void __launch_bounds__(64 * CG_STRUCT_GROUPS) k_structure_reduce(cons
         out[p] = a;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) out[W] = count;
+}
+
+// Momentum distribution (cg_momentum.hpp): n_k^(b) of every walker from its M (ratio, shift) pairs, summed over the rows of the batch.
+// grid (x: workgroups along the rows, y: slices of 256 k vectors), thread <-> k; a workgroup walks its rows one after the other and writes
+// one row of partial sums each; k_structure_reduce sums the rows in the fixed order.  Every thread of a workgroup reads the same
+// (ratio, shift) pair at the same time: no staging.
+template <int D>
+__global__ void __launch_bounds__(256) k_momentum(const double* __restrict__ ratios, const double* __restrict__ shifts, int B, int rows, int M,
+                                                  double invS, const double* __restrict__ K, int nK, double* __restrict__ partial) {
+    const int kidx = blockIdx.y * blockDim.x + threadIdx.x, W = cg_momentum_width(nK);
+    for (int row = blockIdx.x; row < rows; row += gridDim.x)
+        cg_momentum_row<D>(ratios, shifts, B, rows, row, M, invS, K, nK, kidx, partial + (size_t)row * W);
 }
 
 __global__ void k_wrap(double* __restrict__ x, size_t count, double L) {
@@ -381,6 +394,7 @@ void cg_destroy(cg_ctx* c) {
     if (c->d_G) (void)hipFree(c->d_G);
     if (c->d_gk) (void)hipFree(c->d_gk);
     if (c->d_K) (void)hipFree(c->d_K);
+    if (c->d_Km) (void)hipFree(c->d_Km);
     if (c->d_accept) (void)hipFree(c->d_accept);
     if (c->d_rate) (void)hipFree(c->d_rate);
     if (c->ev_a) (void)hipEventDestroy(c->ev_a);
@@ -615,6 +629,65 @@ int cg_structure_sums(cg_ctx* c, const double* x, int B, double* out) {
             hipLaunchKernelGGL((k_structure<3>), grid, dim3(nt), lds, c->stream, (const double*)ax.dev, B, rows, n, c->L, (const int*)c->d_K,
                                c->nK, c->Kmax, c->nbins, scale, partial);
         }
+    }
+    hipLaunchKernelGGL(k_structure_reduce, dim3((W + 63) / 64), dim3(64 * CG_STRUCT_GROUPS), 0, c->stream, (const double*)partial, rows, W, (double)B,
+                       (double*)ao.dev);
+    if ((rc = unstage(c, ao))) return rc;
+    return finish(c);
+}
+
+/* ---- momentum distribution (cg_momentum.hpp) ---- */
+int cg_set_momentum(cg_ctx* c, const double* K, int nK) {
+    if (!c || !K || nK < 1 || nK > (1 << 24)) CG_FAIL(c, CG_ERR_ARG, "cg_set_momentum: bad argument (nK=%d); 1 <= nK <= 2^24, K not NULL", nK);
+    const size_t cnt = (size_t)nK * c->dim;
+    for (size_t e = 0; e < cnt; ++e)
+        if (!std::isfinite(K[e])) CG_FAIL(c, CG_ERR_ARG, "cg_set_momentum: k component %zu is not finite", e);
+    CG_HIP(c, hipSetDevice(c->device));
+    CG_HIP(c, hipStreamSynchronize(c->stream));
+    c->have_momentum = false;
+    if (c->d_Km) { (void)hipFree(c->d_Km); c->d_Km = nullptr; }
+    CG_HIP(c, hipMalloc((void**)&c->d_Km, sizeof(double) * cnt));
+    CG_HIP(c, hipMemcpy(c->d_Km, K, sizeof(double) * cnt, hipMemcpyHostToDevice));
+    c->nKm = nK; c->have_momentum = true;
+    return CG_OK;
+}
+int cg_momentum_size(const cg_ctx* c) {
+    if (!c) return CG_ERR_ARG;
+    if (!c->have_momentum) return CG_ERR_STATE;
+    return 3 * c->nKm + 2;
+}
+int cg_momentum_sums(cg_ctx* c, const double* x, const int32_t* sidx, int B, int S, const double* shifts, uint64_t seed, uint64_t walker_offset,
+                     double* out) {
+    if (!c || B < 0) return CG_ERR_ARG;
+    if (!c->fast) return cg_displaced_launch(c, "cg_momentum_sums", nullptr, nullptr, 0, 0, nullptr, 0, 0, nullptr, nullptr);   // CG_ERR_UNSUPPORTED
+    if (!c->have_momentum) CG_FAIL(c, CG_ERR_STATE, "cg_momentum_sums: cg_set_momentum has not been called");
+    if (!c->have_theta) CG_FAIL(c, CG_ERR_STATE, "cg_momentum_sums: cg_set_flow_params has not been called");
+    if (S < 1 || (long long)S * c->n > 0x7fffffffLL) CG_FAIL(c, CG_ERR_ARG, "cg_momentum_sums: S = %d (need 1 <= S and S n < 2^31)", S);
+    if (!out || (B > 0 && (!x || !sidx))) CG_FAIL(c, CG_ERR_ARG, "cg_momentum_sums: NULL argument");
+    CG_HIP(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = arena_reset(c))) CG_FAIL(c, rc, "cg_momentum_sums: arena");
+    const int n = c->n, D = c->dim, N = n * D, nK = c->nKm, W = cg_momentum_width(nK), rows = cg_structure_rows(B), M = S * n;
+    Arg ax{B > 0 ? (void*)x : nullptr, nullptr, sizeof(double) * (size_t)B * N, true, false};
+    Arg as{B > 0 ? (void*)sidx : nullptr, nullptr, sizeof(int32_t) * (size_t)B * n, true, false};
+    Arg ah{B > 0 ? (void*)shifts : nullptr, nullptr, sizeof(double) * (size_t)B * M * D, true, false};
+    Arg ao{out, nullptr, sizeof(double) * (size_t)(W + 1), false, true};
+    if ((rc = stage(c, ax)) || (rc = stage(c, as)) || (rc = stage(c, ah)) || (rc = stage(c, ao))) return rc;
+    double* partial = nullptr;
+    if (rows > 0) {
+        // ratios, the drawn shifts and the partial rows live in the arena
+        double* ratios = (double*)arena_take(c, sizeof(double) * 2 * (size_t)B * M);
+        double* drawn = ah.dev ? nullptr : (double*)arena_take(c, sizeof(double) * (size_t)B * M * D);
+        partial = (double*)arena_take(c, sizeof(double) * (size_t)rows * W);
+        if (!ratios || (!ah.dev && !drawn) || !partial) CG_FAIL(c, CG_ERR_HIP, "cg_momentum_sums: workspace allocation failed");
+        if ((rc = cg_displaced_launch(c, "cg_momentum_sums", (const double*)ax.dev, (const int*)as.dev, B, S, (const double*)ah.dev, seed, walker_offset,
+                                      ratios, drawn))) return rc;
+        const double* used = ah.dev ? (const double*)ah.dev : drawn;
+        const int nt = 256, want = cg_tune::momentum_grid();
+        const dim3 grid(want > 0 ? std::min(want, rows) : rows, (nK + nt - 1) / nt);
+        const double invS = 1.0 / (double)S;
+        if (D == 2) hipLaunchKernelGGL((k_momentum<2>), grid, dim3(nt), 0, c->stream, (const double*)ratios, used, B, rows, M, invS, (const double*)c->d_Km, nK, partial);
+        else hipLaunchKernelGGL((k_momentum<3>), grid, dim3(nt), 0, c->stream, (const double*)ratios, used, B, rows, M, invS, (const double*)c->d_Km, nK, partial);
     }
     hipLaunchKernelGGL(k_structure_reduce, dim3((W + 63) / 64), dim3(64 * CG_STRUCT_GROUPS), 0, c->stream, (const double*)partial, rows, W, (double)B,
                        (double*)ao.dev);

@@ -69,6 +69,10 @@ struct cg_ctx {
     int nK = 0, Kmax = 0, nbins = 0;
     double rmax = 0;
     int* d_K = nullptr;
+    // momentum distribution (cg_set_momentum): real k vectors in units of 2 pi / L
+    bool have_momentum = false;
+    int nKm = 0;
+    double* d_Km = nullptr;
     int ptr_mode = CG_PTR_HOST;
     int block_threads = 0;
     int cu_count = 256;
@@ -231,6 +235,7 @@ inline int van_grad_reg()            { return cg_env_int("CG_VAN_GRAD_REG", 1); 
 inline int van_static(int B, int cu) { return cg_env_int("CG_VAN_STATIC", B <= 16 * cu ? 1 : 0); }   // sampler / log-probability with compile-time model dimensions
 // structure observables (cg_hip.hip)
 inline int struct_grid()             { return cg_env_int("CG_STRUCT_GRID", 0); }                     // workgroups of cg_structure_sums along the rows (0: one per row; same bits at any value)
+inline int momentum_grid()           { return cg_env_int("CG_MOMENTUM_GRID", 0); }                   // the same for the reduction kernel of cg_momentum_sums
 // solver (cg_solve.inc)
 inline int fisher_slices()           { return cg_env_int("CG_FISHER_SLICES", 0); }                   // batch slices of cg_fisher_real (0: by occupancy)
 inline int chol_quadrant_blocks()    { return cg_env_int("CG_CHOL_QUADRANT_BLOCKS", 1024); }         // fewer 64 x 64 blocks than this: a wave per quadrant (once per process)
@@ -280,4 +285,7 @@ int cg_gen_run_mcmc(cg_ctx* c, double* x, const int* sidx, int B, int steps, dou
 int cg_gen_run_param_vjp(cg_ctx* c, int grid, const double* x, const int* sidx, int B, const double* w_re, const double* w_im,
                          double* partial, double* score);
 int cg_gen_run_grad_lap(cg_ctx* c, int grid, const double* x, const int* sidx, int B, int mode, const double* v, double* grad, double* lap);
+// displaced ratios on device pointers (cg_k_sampler_a.hip): what cg_momentum_sums (cg_hip.hip) runs before its reduction
+int cg_displaced_launch(cg_ctx* c, const char* fn, const double* x, const int* sidx, int B, int S, const double* shifts, uint64_t seed,
+                        uint64_t walker_offset, double* ratios, double* shifts_out);
 extern "C" int cg_fisher_real_nr(cg_ctx* c, const double* S_dev, int B, int P, double* F_dev);

@@ -2,6 +2,8 @@
 // (dim, spsize, tpsize) instantiations.  Included by cg_k_sampler_a.hip / cg_k_sampler_b.hip with
 //   CG_UNIT_CONFIGS(X), CG_UNIT_SPECIALS(X) : the instantiations of this unit     CG_UNIT_NAME(f) : its function prefix
 // Launch functions return 1 (launched), 0 (configuration not in this unit) or a negative error code.
+// With CG_UNIT_DISPLACED defined the unit instantiates k_displaced_ratios alone (cg_k_displaced_a.hip / cg_k_displaced_b.hip: translation units
+// of their own, so that the second family of chain-sized kernels compiles next to the first instead of after it); without it, k_logpsi and k_mcmc.
 template <int D, int HS, int HT, int MAXT>
 __global__ void __launch_bounds__(MAXT, (MAXT <= 256 ? CG_WAVES_PER_EU : 1)) k_logpsi(CgDev m, const double* __restrict__ theta, const double* __restrict__ spk, const double* __restrict__ tab, const double* __restrict__ x, const int* __restrict__ sidx, int B, int mode,
                          double* __restrict__ logphi, double* __restrict__ hld, double* __restrict__ logpsi_out,
@@ -131,10 +133,87 @@ __global__ void __launch_bounds__(MAXT, (MAXT <= 256 ? CG_WAVES_PER_EU : 1)) k_m
     CG_STAMP_FLUSH
 }
 
+// Displaced wave-function ratios for the momentum distribution (cg_momentum.hpp): Psi(x with row i moved by s L) / Psi(x) for M = S n
+// single-particle displacements of every walker.  Built like k_mcmc -- one workgroup per walker, the same LDS image (configuration,
+// trial configuration, staged plane waves, resident weight fragments; the flag slot stays unused), the same instantiations, and the
+// log Psi code once in the instruction stream: evaluation -1 is the base configuration, evaluation m = j n + i moves particle i = m mod n
+// by shifts[b, j, i, :] L (supplied), or by Philox uniforms in [0, 1) (cg_rng.hpp: the counter domain), which are then written to
+// shifts_out as well.  Lane 0 writes ratios[b, m] = (Re, Im) = exp(dRe log Psi) (cos, sin)(dIm log Psi); a non-finite value is written as is.
+template <int D, int HS, int HT, int MAXT, int NS = 0>
+__global__ void __launch_bounds__(MAXT, (MAXT <= 256 ? CG_WAVES_PER_EU : 1)) k_displaced_ratios(CgDev m, const double* __restrict__ theta, const double* __restrict__ spk, const double* __restrict__ tab, const double* __restrict__ x, const int* __restrict__ sidx, int B, int M,
+                       uint64_t seed, uint64_t walker_offset, const double* __restrict__ shifts,
+                       double* __restrict__ shifts_out, double* __restrict__ ratios) {
+    using F = CgFast<D, HS, HT>;
+    double* lds = cg_dyn_lds + CG_TAB_DOUBLES;
+    const CgBlk b{(int)threadIdx.x, NS > 0 ? MAXT : (int)blockDim.x};
+    for (int e = threadIdx.x; e < CG_TAB_DOUBLES; e += blockDim.x) cg_dyn_lds[e] = tab[e];
+    __syncthreads();
+    const int n = NS > 0 ? NS : m.n, N = n * D;
+    CgFastLds lay_s = m.lay;
+    if constexpr (NS > 0) lay_s = cg_fast_layout(NS, D, HS, HT, true, HS == 16 && HT == 16);   // folds to constants
+    const CgFastLds& lay = lay_s;
+    double* xc = lds + lay.total;          // base configuration
+    double* xp = xc + ((N + 1) & ~1);        // displaced configuration
+    double* kv = xp + ((N + 1) & ~1) + 2;    // the walker's n occupied plane waves (the layout of k_mcmc: its flag slot lies in between)
+    CG_STAMP_INIT
+    typename F::WFrag wfrag; const typename F::WFrag* wf = nullptr;
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (HS == 16 && HT == 16) {
+        F::load_frags(theta, wfrag); wf = &wfrag;
+        if (lay.wave_lu && !lay.dual) { F::stage_wt(b, theta, lds, lay); wfrag.wt_resident = true; }
+    }
+#endif
+    for (int w = blockIdx.x; w < B; w += gridDim.x) {
+        const int* si = sidx + (size_t)w * n;
+        for (int e = b.tid; e < N; e += b.nthr) { xc[e] = x[(size_t)w * N + e]; kv[e] = spk[(size_t)si[e / D] * D + e % D]; }
+        b.sync();
+        double base_re = 0.0, base_im = 0.0;
+        int i0 = 0;                            // first coordinate of the particle that evaluation s moves: (s mod n) D
+        // evaluation -1 is the base configuration, through the SAME call site as the displaced ones (see k_mcmc)
+        for (int s = -1; s < M; ++s) {
+            CG_STAMP_START(0)
+            for (int e = b.tid; e < N; e += b.nthr) {
+                double v = xc[e];
+                const int a = e - i0;
+                if (s >= 0 && a >= 0 && a < D) {
+                    const size_t q = ((size_t)w * M + s) * D + a;
+                    const double u = shifts ? shifts[q] : cg_philox_shift_ool(seed, walker_offset + w, (uint32_t)s, (uint32_t)a);
+                    if (shifts_out) shifts_out[q] = u;
+                    v += u * m.L;
+                }
+                xp[e] = v;
+            }
+            b.sync();
+            CG_STAMP(0)
+            double re, im, h;
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(CG_NO_OPAQUE_TID)
+            int tid_o = b.tid; asm volatile("" : "+v"(tid_o));      // opaque lane id, once per evaluation (see k_mcmc)
+            const CgBlk be{tid_o, b.nthr};
+#else
+            const CgBlk& be = b;
+#endif
+            F::template logpsi<F::pair_cache_ok(NS, MAXT) ? NS : 0>(be, theta, xp, kv, nullptr, n, m.L, lds, lay, re, im, h, wf);
+            if (s < 0) { base_re = re + h; base_im = im; }
+            else {
+                if (b.tid == 0) {
+                    const double mag = cg_exp_ool((re + h) - base_re);       // NaN / inf in -> NaN / inf out, as is
+                    const CgSinCos sc = cg_sincos_ool(im - base_im);
+                    ratios[((size_t)w * M + s) * 2] = mag * sc.c; ratios[((size_t)w * M + s) * 2 + 1] = mag * sc.s;
+                }
+                i0 += D; if (i0 >= N) i0 = 0;
+            }
+            b.sync();
+            CG_STAMP_END(15)
+        }
+    }
+    CG_STAMP_FLUSH
+}
+
 
 typedef CG_CFG_LIST(CG_UNIT_CONFIGS) CgUnitConfigs;
 typedef CG_CFG_LIST(CG_UNIT_SPECIALS) CgUnitSpecials;
 
+#if !defined(CG_UNIT_DISPLACED)
 int CG_UNIT_NAME(logpsi)(cg_ctx* c, int nt, size_t lds, const CgDev& m, const double* x, const int* sidx, int B, int mode,
                          double* logphi, double* hld, double* logpsi_out, double* logp_out, double* z_out, double* J_out) {
     return cg_with_config<CgUnitConfigs>(c->dim, c->hs, c->ht, [&](auto cfg) -> int {
@@ -166,3 +245,22 @@ int CG_UNIT_NAME(mcmc)(cg_ctx* c, int nt, size_t lds, const CgDev& m, double* x,
         return cg_with_nt_upto<256, 512, 1024>(nt, [&](auto ntc) -> int { return launch(cfg, ntc, std::integral_constant<int, 0>{}); });
     });
 }
+#else
+int CG_UNIT_NAME(displaced)(cg_ctx* c, int nt, size_t lds, const CgDev& m, const double* x, const int* sidx, int B, int M,
+                            uint64_t seed, uint64_t walker_offset, const double* shifts, double* shifts_out, double* ratios) {
+    // the instantiations of k_mcmc: (MAXT, NS) as there
+    auto launch = [&](auto cfg, auto maxt, auto ns) -> int {
+        constexpr int D = cfg.D, HS = cfg.HS, HT = cfg.HT, MAXT = maxt, NS = ns;
+        if (int rc = set_lds(c, k_displaced_ratios<D, HS, HT, MAXT, NS>, lds)) return rc;
+        hipLaunchKernelGGL((k_displaced_ratios<D, HS, HT, MAXT, NS>), dim3(B), dim3(nt), lds, c->stream, m, (const double*)c->d_theta, (const double*)c->d_spk,
+                           (const double*)c->d_tab, x, sidx, B, M, seed, walker_offset, shifts, shifts_out, ratios);
+        return 1;
+    };
+    if (int rc = cg_with_special<CgUnitSpecials>(c->dim, c->hs, c->ht, c->n, nt, [&](auto cfg) -> int {
+            return launch(cfg, std::integral_constant<int, cfg.NT>{}, std::integral_constant<int, cfg.N>{});
+        })) return rc;
+    return cg_with_config<CgUnitConfigs>(c->dim, c->hs, c->ht, [&](auto cfg) -> int {
+        return cg_with_nt_upto<256, 512, 1024>(nt, [&](auto ntc) -> int { return launch(cfg, ntc, std::integral_constant<int, 0>{}); });
+    });
+}
+#endif

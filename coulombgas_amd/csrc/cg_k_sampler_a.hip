@@ -12,6 +12,27 @@ int cg_sampler_b_logpsi(cg_ctx* c, int nt, size_t lds, const CgDev& m, const dou
                         double* logphi, double* hld, double* logpsi_out, double* logp_out, double* z_out, double* J_out);
 int cg_sampler_b_mcmc(cg_ctx* c, int nt, size_t lds, const CgDev& m, double* x, const int* sidx, int B, int mc_steps, double mc_stddev,
                       uint64_t seed, uint64_t walker_offset, const double* noise, const double* unif, double* logp_out);
+// (cg_k_displaced_a.hip / cg_k_displaced_b.hip)
+int cg_sampler_a_displaced(cg_ctx* c, int nt, size_t lds, const CgDev& m, const double* x, const int* sidx, int B, int M,
+                           uint64_t seed, uint64_t walker_offset, const double* shifts, double* shifts_out, double* ratios);
+int cg_sampler_b_displaced(cg_ctx* c, int nt, size_t lds, const CgDev& m, const double* x, const int* sidx, int B, int M,
+                           uint64_t seed, uint64_t walker_offset, const double* shifts, double* shifts_out, double* ratios);
+
+// k_displaced_ratios on device pointers (cg_displaced_ratios below and cg_momentum_sums in cg_hip.hip): M = S n evaluations per walker
+int cg_displaced_launch(cg_ctx* c, const char* fn, const double* x, const int* sidx, int B, int S, const double* shifts, uint64_t seed,
+                        uint64_t walker_offset, double* ratios, double* shifts_out) {
+    if (!c->fast)
+        CG_FAIL(c, CG_ERR_UNSUPPORTED, "%s: displaced ratios run on the depth-2 fast path only (depth=%d spsize=%d tpsize=%d dim=%d is not one of its "
+                "configurations)", fn, c->depth, c->hs, c->ht, c->dim);
+    const int N = c->n * c->dim, nt = threads_of(c);
+    const size_t lds = sizeof(double) * (CG_TAB_DOUBLES + c->lay.total + 3 * ((N + 1) & ~1) + 2);   // the LDS image of k_mcmc
+    const CgDev m = make_dev(c);
+    int rc;
+    if ((rc = cg_sampler_a_displaced(c, nt, lds, m, x, sidx, B, S * c->n, seed, walker_offset, shifts, shifts_out, ratios)) < 0) return rc;
+    if (rc == 0 && (rc = cg_sampler_b_displaced(c, nt, lds, m, x, sidx, B, S * c->n, seed, walker_offset, shifts, shifts_out, ratios)) < 0) return rc;
+    if (rc != 1) CG_FAIL(c, CG_ERR_UNSUPPORTED, "%s: configuration not instantiated", fn);
+    return CG_OK;
+}
 
 extern "C" {
 
@@ -108,6 +129,28 @@ int cg_mcmc(cg_ctx* c, double* x, const int32_t* sidx, int B, int mc_steps, doub
     if ((rc = finish(c))) return rc;
     if (n_accept) return cg_mcmc_accepts(c, n_accept);
     return CG_OK;
+}
+
+int cg_displaced_ratios(cg_ctx* c, const double* x, const int32_t* sidx, int B, int S, const double* shifts, uint64_t seed,
+                        uint64_t walker_offset, double* ratios, double* shifts_out) {
+    if (c && !c->fast) return cg_displaced_launch(c, "cg_displaced_ratios", nullptr, nullptr, 0, 0, nullptr, 0, 0, nullptr, nullptr);   // CG_ERR_UNSUPPORTED
+    int rc = check_ready(c, "cg_displaced_ratios", B); if (rc) return rc;
+    if (S < 1 || (long long)S * c->n > 0x7fffffffLL) CG_FAIL(c, CG_ERR_ARG, "cg_displaced_ratios: S = %d (need 1 <= S and S n < 2^31)", S);
+    if (B == 0) return CG_OK;
+    if (!x || !sidx || !ratios) CG_FAIL(c, CG_ERR_ARG, "cg_displaced_ratios: NULL argument");
+    const int n = c->n, N = n * c->dim;
+    if ((rc = arena_reset(c))) CG_FAIL(c, rc, "cg_displaced_ratios: arena");
+    Arg ax{(void*)x, nullptr, sizeof(double) * (size_t)B * N, true, false};
+    Arg as{(void*)sidx, nullptr, sizeof(int32_t) * (size_t)B * n, true, false};
+    Arg ah{(void*)shifts, nullptr, sizeof(double) * (size_t)B * S * N, true, false};
+    Arg ar{ratios, nullptr, sizeof(double) * 2 * (size_t)B * S * n, false, true};
+    Arg ao{shifts_out, nullptr, sizeof(double) * (size_t)B * S * N, false, true};
+    Arg* all[] = {&ax, &as, &ah, &ar, &ao};
+    for (Arg* a : all) if ((rc = stage(c, *a))) return rc;
+    if ((rc = cg_displaced_launch(c, "cg_displaced_ratios", (const double*)ax.dev, (const int*)as.dev, B, S, (const double*)ah.dev, seed, walker_offset,
+                                  (double*)ar.dev, (double*)ao.dev))) return rc;
+    for (Arg* a : all) if ((rc = unstage(c, *a))) return rc;
+    return finish(c);
 }
 
 }  // extern "C"

@@ -32,6 +32,15 @@ CG_DEVI double cg_philox_uniform(uint64_t seed, uint64_t walker, uint32_t step) 
     double u1, u2; cg_philox_uniform2(seed, walker, step, 0xFFFFFFFFu, u1, u2);
     return u2;
 }
+// Counter domains (c = {walker lo, walker hi, step, item}, key = seed): the Metropolis chains use step < mc_steps < 2^31 with
+// item < n * dim (proposal normals) or item = 0xFFFFFFFF (accept uniform); cg_randn uses step = 0x5eed, item = 0 with walker = the
+// element index.  The displacements of k_displaced_ratios live where no chain reaches: step = 0x80000000 | m (m < 2^31 the evaluation
+// index j n + i), item = axis < dim, walker = walker_offset + b; the uniform is u_half, in [0, 1).
+#define CG_PHILOX_SHIFT_DOMAIN 0x80000000u
+CG_DEVI double cg_philox_shift(uint64_t seed, uint64_t walker, uint32_t m, uint32_t axis) {
+    double u1, u2; cg_philox_uniform2(seed, walker, CG_PHILOX_SHIFT_DOMAIN | m, axis, u1, u2);
+    return u2;
+}
 // Out-of-line versions for the depth-2 sampler kernel (one call per coordinate and Metropolis step): the Philox key
 // schedule and the constants of log / sincos / sqrt stay inside the callee instead of being hoisted out of the chain
 // loop and spilled (see CG_OUTLINE in cg_common.hpp for why only that kernel uses them).
@@ -41,5 +50,8 @@ static CG_OUTLINE double cg_philox_normal_ool(uint64_t seed, uint64_t walker, ui
 }
 static CG_OUTLINE double cg_philox_uniform_ool(uint64_t seed, uint64_t walker, uint32_t step) {
     return cg_philox_uniform(seed, walker, step);
+}
+static CG_OUTLINE double cg_philox_shift_ool(uint64_t seed, uint64_t walker, uint32_t m, uint32_t axis) {
+    return cg_philox_shift(seed, walker, m, axis);
 }
 #endif

@@ -174,14 +174,16 @@ def format_row(i, data, rs, batch_total, acc_steps, accept_rate):
 def train(flow, params_flow, sp_indices, n, dim, L, rs, beta, batch, epochs, sampler, log_prob, params_van=None,
           optimizer=None, sr=None, kappa=10, Gmax=15, mc_therm=10, mc_steps=50, mc_stddev=0.1, acc_steps=1,
           hutchinson=True, seed=42, log=None, log_prob_vjp=None, classical_score_fn=None, comm=None, device_resident=True,
-          ckpt_path=None, ckpt_every=100, epoch_finished=0, structure=None):
+          ckpt_path=None, ckpt_every=100, epoch_finished=0, structure=None, momentum=None):
     """main.py:216-384 on one rank.  sr = (damping, max_norm) selects hybrid_fisher_sr (main.py:179-184), otherwise
     `optimizer` (default adam(1e-3)).  Returns (params_van, params_flow, rows) with rows the data.txt lines.
     ckpt_path / ckpt_every / epoch_finished: the checkpoints of main.py:374-381 ({"keys", "x", "params_van", "params_flow",
     "opt_state"}, x with the reference's leading device axis) and the resume of main.py:217-223 (a shipped epoch_*.pkl
     resumes too).  device_resident: walkers, local energies, scores and Fisher matrices stay in HBM for the whole run.
     structure: an accumulator from make_structure_observable; every sampling call of the epoch loop (not the thermalisation rounds)
-    adds its walkers to it, on the device.  None: nothing is called or allocated for it."""
+    adds its walkers to it, on the device.  None: nothing is called or allocated for it.
+    momentum: an accumulator from make_momentum_observable, fed the walkers and state indices of the same sampling calls (shifts_per_particle
+    x n further log Psi evaluations per walker and call, with the flow parameters the call sampled with).  None: likewise nothing."""
     cm = comm or get_comm()
     if log_prob_vjp is None and hasattr(log_prob, "vjp"):          # make_autoregressive_sampler's log_prob carries its own
         log_prob_vjp = log_prob.vjp                                 # reverse pass: the density matrix is trained as well
@@ -256,6 +258,8 @@ def train(flow, params_flow, sp_indices, n, dim, L, rs, beta, batch, epochs, sam
             accept_acc += accept_rate
             if structure is not None:
                 structure.accumulate(x)
+            if momentum is not None:
+                momentum.accumulate(x, state_indices)
             params_van, params_flow, opt_state, acc = update(params_van, params_flow, opt_state, state_indices, x,
                                                              key.spawn(1)[0], acc, a == acc_steps - 1)
         row = format_row(i, acc["data"], rs, batch * cm.world, acc_steps, accept_acc / acc_steps)

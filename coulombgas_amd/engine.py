@@ -198,6 +198,21 @@ class Engine:
             raise _lib.CoulombGasError(size, "cg_structure_size: cg_set_structure has not been called")
         return int(size)
 
+    def set_momentum(self, K):
+        """k vectors (nK, dim), real, units of 2 pi / L, of momentum_sums (cg_set_momentum)"""
+        K = _f64(K).reshape(-1, self.dim)
+        key = K.tobytes()
+        if getattr(self, "_momentum", None) != key:
+            check(lib().cg_set_momentum(self._ctx, _p(K), K.shape[0]), self._ctx)
+            self._momentum = key
+
+    def momentum_size(self):
+        """length of the packed vector of momentum_sums: 3 nK + 2"""
+        size = lib().cg_momentum_size(self._ctx)
+        if size < 0:
+            raise _lib.CoulombGasError(size, "cg_momentum_size: cg_set_momentum has not been called")
+        return int(size)
+
     def device_mode(self, on=True):
         self._mode = _lib.CG_PTR_DEVICE if on else _lib.CG_PTR_HOST
         check(lib().cg_set_pointer_mode(self._ctx, self._mode), self._ctx)
@@ -311,6 +326,36 @@ class Engine:
         xb, _ = self._xb(x)
         out = np.empty(self.structure_size())
         check(lib().cg_structure_sums(self._ctx, _p(xb), xb.shape[0], _p(out)), self._ctx)
+        return out
+
+    def _shifts(self, shifts, B, S):
+        if shifts is None:
+            return None
+        shifts = _f64(shifts)
+        if shifts.shape != (B, S, self.n, self.dim):
+            raise ValueError("shifts must have shape %s, got %s" % ((B, S, self.n, self.dim), shifts.shape))
+        return shifts
+
+    def displaced_ratios(self, x, state_idx, S, shifts=None, seed=0, walker_offset=0):
+        """-> ratios (B, S, n) complex, shifts (B, S, n, dim): Psi(x with row i moved by shifts[b, j, i] L) / Psi(x) (cg_displaced_ratios).
+        shifts None: S Philox uniforms in [0, 1) per particle, axis and walker, returned as drawn."""
+        xb, _ = self._xb(x)
+        B, S = xb.shape[0], int(S)
+        s = self._sb(state_idx, B)
+        sh = self._shifts(shifts, B, S)
+        r = np.empty((B, max(S, 0), self.n, 2))
+        so = np.empty((B, max(S, 0), self.n, self.dim))
+        check(lib().cg_displaced_ratios(self._ctx, _p(xb), _p(s), B, S, _p(sh), int(seed) & (2 ** 64 - 1), int(walker_offset), _p(r), _p(so)), self._ctx)
+        return r[..., 0] + 1j * r[..., 1], so
+
+    def momentum_sums(self, x, state_idx, S, shifts=None, seed=0, walker_offset=0):
+        """packed sums over the batch of n_k^(b), (Re n_k^(b))^2, the dropped terms and the walker count (cg_momentum_sums)"""
+        xb, _ = self._xb(x)
+        B, S = xb.shape[0], int(S)
+        s = self._sb(state_idx, B)
+        sh = self._shifts(shifts, B, S)
+        out = np.empty(self.momentum_size())
+        check(lib().cg_momentum_sums(self._ctx, _p(xb), _p(s), B, S, _p(sh), int(seed) & (2 ** 64 - 1), int(walker_offset), _p(out)), self._ctx)
         return out
 
     def grad_laplacian(self, x, state_idx, mode=_lib.CG_LAP_EXACT, v=None):
@@ -520,6 +565,29 @@ class Engine:
         size = self.structure_size()
         out = self.scratch("structure", (size,))
         self._dev_call(lib().cg_structure_sums, x_d.ptr, int(x_d.shape[0]), out.ptr)
+        out.version += 1
+        if acc is None:
+            return out
+        return self.axpby_d(1.0, out, 1.0, acc, count=size)
+
+    def displaced_ratios_d(self, x_d, sidx_d, S, shifts_d=None, seed=0, walker_offset=0):
+        """cg_displaced_ratios of device-resident walkers -> (ratios (B, S, n) complex pairs, shifts (B, S, n, dim)) in the scratch arrays
+        "disp_ratios" / "disp_shifts" (the shifts as used: drawn in the kernel when shifts_d is None)"""
+        B, S = int(x_d.shape[0]), int(S)
+        r = self.scratch("disp_ratios", (B, S, self.n), complex_pairs=True)
+        so = self.scratch("disp_shifts", (B, S, self.n, self.dim))
+        self._dev_call(lib().cg_displaced_ratios, x_d.ptr, sidx_d.ptr, B, S, shifts_d.ptr if shifts_d is not None else None,
+                       int(seed) & (2 ** 64 - 1), int(walker_offset), r.ptr, so.ptr)
+        r.version += 1; so.version += 1
+        return r, so
+
+    def momentum_sums_d(self, x_d, sidx_d, S, shifts_d=None, seed=0, walker_offset=0, acc=None):
+        """cg_momentum_sums of device-resident walkers into the scratch array "momentum"; with acc (a DeviceArray of the same size) the
+        sums are added into it on the device and acc is returned"""
+        size = self.momentum_size()
+        out = self.scratch("momentum", (size,))
+        self._dev_call(lib().cg_momentum_sums, x_d.ptr, sidx_d.ptr, int(x_d.shape[0]), int(S), shifts_d.ptr if shifts_d is not None else None,
+                       int(seed) & (2 ** 64 - 1), int(walker_offset), out.ptr)
         out.version += 1
         if acc is None:
             return out

@@ -140,6 +140,38 @@ int cg_structure_size(const cg_ctx* ctx);
  * states the order).  NaN in -> NaN in the rho sums the walker enters, its pairs in the overflow bin; never aborts. */
 int cg_structure_sums(cg_ctx* ctx, const double* x, int B, double* out);
 
+/* ---- momentum distribution --------------------------------------------------------------- */
+
+/* Displaced wave-function ratios, the ingredient of every off-diagonal one-body observable.  For each walker b, each of S shifts j and
+ * each particle i:   ratios[b, j, i] = Psi_K(x_b with row i moved by shifts[b, j, i, :] L) / Psi_K(x_b)   as (Re, Im)
+ *                                    = exp(d Re log Psi) (cos, sin)(d Im log Psi),  log Psi as cg_logpsi returns it (1/2 log|det J| included).
+ * x (B,n,dim); state_idx (B,n); shifts (B,S,n,dim) in units of L, or NULL: Philox uniforms in [0, 1) per (walker_offset + b, j n + i, axis)
+ * under `seed` (a counter domain no Metropolis chain uses: csrc/cg_rng.hpp); ratios (B,S,n,2); shifts_out (B,S,n,dim) or NULL receives the
+ * shifts as used (supplied or drawn).  One workgroup per walker, S n + 1 log Psi evaluations each, built like the chain of cg_mcmc (same
+ * LDS image, same instantiations).  Both pointer modes.  A non-finite base value or ratio is written as is: NaN in -> NaN out, never
+ * aborts.  CG_ERR_ARG: S < 1 or S n >= 2^31, NULL x / state_idx / ratios; CG_ERR_STATE: no flow parameters; CG_ERR_UNSUPPORTED: a flow
+ * that is not on the depth-2 fast path.  B == 0 does nothing. */
+int cg_displaced_ratios(cg_ctx* ctx, const double* x, const int32_t* state_idx, int B, int S, const double* shifts, uint64_t seed,
+                        uint64_t walker_offset, double* ratios, double* shifts_out);
+/* K: HOST pointer, nK x dim real vectors in units of 2 pi / L (e.g. rows of the twisted orbital table: k and the orbitals then carry the
+ * same twist and the summand below is periodic in the shift).  CG_ERR_ARG: NULL, nK < 1 or > 2^24, a non-finite component. */
+int cg_set_momentum(cg_ctx* ctx, const double* K, int nK);
+/* 3 nK + 2; CG_ERR_STATE before cg_set_momentum */
+int cg_momentum_size(const cg_ctx* ctx);
+/* Momentum distribution of a walker batch: cg_displaced_ratios (ratios and drawn shifts stay in the library's workspace) and, per walker,
+ *   n_k^(b) = (1/S) sum_{j < S} sum_{i < n} exp(-2 pi i k.s_{b,j,i}) ratios[b, j, i]      (terms in ascending j n + i);
+ * a term whose ratio is not finite adds nothing and is counted.  out (cg_momentum_size) doubles, SUMS over the batch, not means:
+ *   [0, 2 nK)       sum_b n_k^(b) as (re, im) pairs
+ *   [2 nK, 3 nK)    sum_b (Re n_k^(b))^2
+ *   [3 nK]          dropped terms
+ *   [3 nK + 1]      number of walkers summed (B)
+ * so that cg_axpby(1, out, 1, acc) accumulates over calls, one cg_allreduce_sum reduces over ranks, and the accumulated vector normalises
+ * itself: n_k = out[2k] / count, standard error over walkers from out[2 nK + k].  Arguments as cg_displaced_ratios.  Both pointer modes.
+ * B == 0 writes zeros.  Fixed summation order (csrc/cg_momentum.hpp states it), no floating-point atomics: two calls on the same input
+ * agree bit for bit.  CG_ERR_STATE: no cg_set_momentum or no flow parameters; CG_ERR_ARG / CG_ERR_UNSUPPORTED as cg_displaced_ratios. */
+int cg_momentum_sums(cg_ctx* ctx, const double* x, const int32_t* state_idx, int B, int S, const double* shifts, uint64_t seed,
+                     uint64_t walker_offset, double* out);
+
 /* ---- local energy ingredients ------------------------------------------------------------ */
 
 /* grad (B,n,dim,2) complex, lap (B,2) complex of log Psi w.r.t. x:
