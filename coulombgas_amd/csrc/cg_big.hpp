@@ -219,12 +219,17 @@ struct CgBig {
         return l;
     }
 
-    // mode: CG_LAP_HUTCHINSON (1) or CG_LAP_HUTCHINSON_SPLIT (2); the exact mode keeps the first-generation kernel
-    static LayG layout_gradlap(int n, int nthr, int mode, size_t lds_cap_doubles) {
+    // mode: CG_LAP_HUTCHINSON (1) or CG_LAP_HUTCHINSON_SPLIT (2); the exact mode keeps the first-generation kernel.
+    // reenter (cg_grad_laplacian_probes with more than one probe): the jet pass runs once per probe, so every array it reads and does
+    // not itself produce -- sg1, sg2, U, V, Bm, U' next to sh, ch, J^-T, g, T^a, K^ab, which live that long anyway -- lives to PH_END
+    // instead of ending at the phase of the pass that reads it last; the tangent arrays and the jet pool may then overlay each other
+    // and J' as before (each pass writes them before it reads them, and a barrier separates the passes), but none of the above.
+    static LayG layout_gradlap(int n, int nthr, int mode, size_t lds_cap_doubles, bool reenter = false) {
         const size_t N = (size_t)n * D;
         LayG l; memset(&l, 0, sizeof(l));
         CgPlan pl;
-        plan_common(pl, l.c, n, nthr, PH_FWD, PH_DENSE, PH_JD);
+        const int JB_ = reenter ? PH_END : PH_JB, JC_ = reenter ? PH_END : PH_JC, JD_ = reenter ? PH_END : PH_JD;
+        plan_common(pl, l.c, n, nthr, PH_FWD, PH_DENSE, JD_);
         CgFastLds& o = l.c.o;
         const int nw = l.c.nw;
         const bool phi2 = mode == 1;            // the probe pass needs g, T^a, diag K^ab (v^T hess(log phi) v through z', z'')
@@ -232,9 +237,9 @@ struct CgBig {
         pl.add(l.c.J, N * N, PH_JAC, PH_SLATER, 0);
         pl.add(o.m0, (size_t)n * P, PH_PAIRS, PH_DENSE, 100, true); pl.add(o.m1, (size_t)n * HT, PH_PAIRS, PH_DENSE, 100, true);
         pl.add(o.s1, (size_t)n * HS, PH_DENSE, PH_DENSE, 100, true); pl.add(o.s2, (size_t)n * HS, PH_DENSE, PH_DENSE, 100, true);
-        pl.add(o.sg1, (size_t)n * HS, PH_DENSE, PH_JB, 90, true); pl.add(o.sg2, (size_t)n * HS, PH_DENSE, PH_JB, 90, true);
-        pl.add(o.U, N * HS, PH_FACT, PH_JAC, 100, true); pl.add(l.Uk, N * HS, PH_JAC, PH_JC, 50);
-        pl.add(o.V, (size_t)n * F::SPV, PH_FACT, PH_JD, 90, true); pl.add(o.Bm, (size_t)n * F::SPB, PH_FACT, PH_JD, 90, true);
+        pl.add(o.sg1, (size_t)n * HS, PH_DENSE, JB_, 90, true); pl.add(o.sg2, (size_t)n * HS, PH_DENSE, JB_, 90, true);
+        pl.add(o.U, N * HS, PH_FACT, PH_JAC, 100, true); pl.add(l.Uk, N * HS, PH_JAC, JC_, 50);
+        pl.add(o.V, (size_t)n * F::SPV, PH_FACT, JD_, 90, true); pl.add(o.Bm, (size_t)n * F::SPB, PH_FACT, JD_, 90, true);
         pl.add(o.G, (size_t)n * F::SPG, PH_FACT, PH_PASSA, 90, true);
         pl.add(l.c.zb, 2 * N, PH_INV, PH_JE, 95, true);
         pl.add(l.c.Kd, 2 * (size_t)D * D * n, PH_INV, phi2 ? PH_JE : PH_SLATER, 95, true);
@@ -1618,11 +1623,15 @@ struct CgBig {
         CG_STAMP_END(19)
     }
 
+    // MP (cg_grad_laplacian_probes): nprobe probes v + k vstride for this walker behind one set-up, combined by the rule of
+    // cg_probe_add / cg_probe_fold (cg_lap.hpp); l is the re-entrant plan (layout_gradlap(..., reenter = true)) when nprobe > 1
+    template <bool MP = false>
     static __device__ __forceinline__ void grad_laplacian(const CgBlk& b, const double* __restrict__ th, const double* __restrict__ xg,
                                                           const double* __restrict__ spk, const int* __restrict__ sidx, int n, double L,
                                                           int mode, const double* __restrict__ v, double* __restrict__ grad /*N x 2*/,
                                                           double* __restrict__ lap /*2*/, double* lds, double* ws, const LayG& l,
-                                                          double* stash = nullptr, const Stash* st = nullptr) {
+                                                          double* stash = nullptr, const Stash* st = nullptr,
+                                                          int nprobe = 1, size_t vstride = 0, double weight = 1.0) {
         const CgPl pl{lds, ws};
         const LayC& c = l.c;
         typename F::WFrag wf;
@@ -1665,7 +1674,16 @@ struct CgBig {
         reverse_x(b, th, n, L, pl, l, grad);
         CG_STAMP_END(22)
         CG_STAMP_START(24)
-        {
+        if (MP) {
+            double acc[4];
+            for (int k = 0; k < nprobe; ++k) {
+                double r[4];
+                if (k) b.sync();                     // the traces of the last pass are read: this one may overwrite J' and the tangents
+                jet_part(b, th, n, L, pl, l, v + (size_t)k * vstride, mode == 1, r);
+                cg_probe_add(acc, r, k);
+            }
+            cg_probe_fold(tot, acc, weight);
+        } else {
             double r[4];
             jet_part(b, th, n, L, pl, l, v, mode == 1, r);
             tot[0] += r[0]; tot[1] += r[1]; tot[2] += r[2]; tot[3] += r[3];

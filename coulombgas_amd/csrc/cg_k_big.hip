@@ -110,6 +110,51 @@ int cg_big_grad_lap(cg_ctx* c, const CgDev& m, const double* x, const int* sidx,
     });
 }
 
+// cg_grad_laplacian_probes: k_gradlap_big with the probe loop around its jet pass (an instantiation of its own: k_gradlap_big keeps its
+// code).  v is (nprobe, B, n, dim): probe k of walker w at v + (k B + w) N.
+template <int D, int HS, int HT, int NT>
+__global__ void __launch_bounds__(NT, NT <= 256 ? 2 : 1) k_gradlap_big_probes(CgDev m, const double* __restrict__ theta, const double* __restrict__ spk, const double* __restrict__ tab,
+                              const double* __restrict__ x, const int* __restrict__ sidx, int B, int w0, int mode, int nprobe, double weight,
+                              const double* __restrict__ v, double* __restrict__ grad, double* __restrict__ lap, double* ws,
+                              typename CgBig<D, HS, HT>::LayG lay) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    double* lds = cg_dyn_lds + CG_TAB_DOUBLES;
+    const CgBlk b{(int)threadIdx.x, (int)blockDim.x};
+    for (int e = threadIdx.x; e < CG_TAB_DOUBLES; e += blockDim.x) cg_dyn_lds[e] = tab[e];
+    __syncthreads();
+    CG_STAMP_INIT
+    const int n = m.n, N = n * D, w = w0 + blockIdx.x;
+    if (w < B) CgBig<D, HS, HT>::template grad_laplacian<true>(b, theta, x + (size_t)w * N, spk, sidx + (size_t)w * n, n, m.L, mode, v + (size_t)w * N,
+                                                               grad + (size_t)w * N * 2, lap + 2 * w, lds, ws + (size_t)blockIdx.x * lay.ws_total, lay,
+                                                               nullptr, nullptr, nprobe, (size_t)B * N, weight);
+    CG_STAMP_FLUSH
+#endif
+}
+
+// nprobe probes per walker behind one set-up (Hutchinson modes): 1 launched, 0 not served (the caller combines single-probe launches),
+// < 0 error.  One probe runs in the plan of cg_big_grad_lap; more run in the re-entrant plan, which keeps what the jet pass reads alive.
+int cg_big_grad_lap_probes(cg_ctx* c, const CgDev& m, const double* x, const int* sidx, int B, int mode, int nprobe, const double* v, double weight,
+                           double* grad, double* lap) {
+    constexpr int D = 2, HS = 16, HT = 16;
+    if (c->dim != D || c->hs != HS || c->ht != HT || (mode != 1 && mode != 2) || !v || c->n <= 16) return 0;
+    if (cg_tune::big() == 0 || cg_tune::big_lap() == 0) return 0;
+    const int n = c->n;
+    const CgBigShape sh = big_shape(c, D, B);
+    const auto bl = CgBig<D, HS, HT>::layout_gradlap(n, sh.nt, mode, sh.cap, nprobe > 1);
+    if (cg_tune::big_debug())
+        fprintf(stderr, "cg_big_grad_lap_probes n=%d nt=%d mode=%d nprobe=%d ok=%d lds %u doubles, ws %u doubles per workgroup; J %d JT %d Ta %d Uk %d jp %d Vt %d Bmt %d Upt %d Jp %d\n",
+                n, sh.nt, mode, nprobe, bl.ok, bl.lds_total, bl.ws_total, bl.c.J, bl.c.JT, bl.Ta, bl.Uk, bl.jp, bl.Vt, bl.Bmt, bl.Upt, bl.Jp);
+    if (!bl.ok) return 0;
+    const size_t lds = sizeof(double) * (CG_TAB_DOUBLES + (size_t)bl.lds_total);
+    return cg_with_nt_equal<256, 512>(sh.nt, [&](auto ntc) -> int {
+        constexpr int NT = ntc;
+        return cg_launch_chunked(c, k_gradlap_big_probes<D, HS, HT, NT>, lds, bl.ws_total, 8, sh.chunk, B, [&](int grid, int w0) {
+            hipLaunchKernelGGL((k_gradlap_big_probes<D, HS, HT, NT>), dim3(grid), dim3(NT), lds, c->stream, m, (const double*)c->d_theta,
+                               (const double*)c->d_spk, (const double*)c->d_tab, x, sidx, B, w0, mode, nprobe, weight, v, grad, lap, (double*)c->ws, bl);
+        });
+    });
+}
+
 // Both at once for the optimisation step (src/VMC.py:35 and the jacrev of main.py:278 on the same walkers): the set-up -- flow, Jacobian,
 // the two inverses, g: 60 % of k_scores_big -- runs once; the grad / Laplacian part parks what the score passes need in the workspace
 // (CgBig::Stash), then the score passes run in their own layout.  Results: those of the two kernels, bit for bit.

@@ -44,6 +44,32 @@ __global__ void __launch_bounds__(NT, NT <= 256 ? 2 : 1) k_grad_lap2(CgDev m, co
     CG_STAMP_FLUSH
 }
 
+// cg_grad_laplacian_probes at the sizes whose every array lives in LDS: k_grad_lap2<AL = true> with the probe loop around its jet pass
+// (an instantiation of its own: k_grad_lap2 keeps its code).  v is (nprobe, B, n, dim): probe k of walker w at v + (k B + w) N.
+template <int D, int HS, int HT>
+__global__ void __launch_bounds__(256, 2) k_grad_lap2_probes(CgDev m, const double* __restrict__ theta, const double* __restrict__ spk, const double* __restrict__ tab, const double* __restrict__ x, const int* __restrict__ sidx, int B, int mode,
+                           int nprobe, double weight, const double* __restrict__ v, double* __restrict__ grad, double* __restrict__ lap,
+                           double* ws, typename CgLap<D, HS, HT>::Lay lay) {
+    double* lds = cg_dyn_lds + CG_TAB_DOUBLES;
+    const CgBlk b{(int)threadIdx.x, (int)blockDim.x};
+    for (int e = threadIdx.x; e < CG_TAB_DOUBLES; e += blockDim.x) cg_dyn_lds[e] = tab[e];
+    const int n = m.n, N = n * D;
+    const double* th = theta;
+    if (lay.th_lds) {                    // (always, on this path: the branch keeps the pointer generic, as in k_grad_lap2)
+        double* th_l = lds + lay.th;
+        for (int e = b.tid; e < CgFast<D, HS, HT>::NPARAM; e += b.nthr) th_l[e] = theta[e];
+        th = th_l;
+    }
+    __syncthreads();
+    CG_STAMP_INIT
+    const int w = blockIdx.x;
+    if (w < B)
+        CgLap<D, HS, HT>::template grad_laplacian<true, true>(b, th, x + (size_t)w * N, spk, sidx + (size_t)w * n, n, m.L, mode, v + (size_t)w * N,
+                                                              grad + (size_t)w * N * 2, lap + 2 * w, lds, ws, lay, nullptr, nullptr,
+                                                              nprobe, (size_t)B * N, weight);
+    CG_STAMP_FLUSH
+}
+
 // Per-sample scores, second generation (cg_score.hpp): one walker per workgroup, every array in LDS, the score row written as
 // (re, im) pairs.  Launched for the systems whose layout fits the LDS budget (n <= 16); k_param_vjp below serves the others.
 #ifndef CG_SCORE_LDS_BYTES
@@ -123,6 +149,30 @@ int CG_UNIT_NAME(grad_lap)(cg_ctx* c, const CgDev& m, const double* x, const int
                                    (const double*)c->d_tab, x, sidx, B, w0, mode, v, grad, lap, (double*)c->ws, dl);
             });
         });
+    });
+}
+
+// nprobe probes per walker behind one set-up (modes 1 and 2): 1 launched, 0 this unit has no probe-loop kernel for the configuration and
+// size (the caller then combines single-probe launches), < 0 error.  Served: everything in LDS (any configuration of the unit), and the
+// planned kernel of the (dim 2, 16, 16) flow at n > 16.
+int cg_big_grad_lap_probes(cg_ctx* c, const CgDev& m, const double* x, const int* sidx, int B, int mode, int nprobe, const double* v, double weight,
+                           double* grad, double* lap);      // cg_k_big.hip
+int CG_UNIT_NAME(grad_lap_probes)(cg_ctx* c, const CgDev& m, const double* x, const int* sidx, int B, int mode, int nprobe, const double* v,
+                                  double weight, double* grad, double* lap) {
+    return cg_with_config<CgUnitConfigs>(c->dim, c->hs, c->ht, [&](auto cfg) -> int {
+        constexpr int D = cfg.D, HS = cfg.HS, HT = cfg.HT;
+        int rc;
+        const auto dl = CgLap<D, HS, HT>::layout(c->n, 256, mode, (size_t)CG_LAP_LDS_BYTES / sizeof(double) - CG_TAB_DOUBLES);
+        if (dl.all_lds && dl.th_lds) {
+            const size_t lds = sizeof(double) * (CG_TAB_DOUBLES + (size_t)dl.lds_total);
+            if ((rc = ensure_ws(c, 64))) return rc;
+            if ((rc = set_lds(c, k_grad_lap2_probes<D, HS, HT>, lds))) return rc;
+            hipLaunchKernelGGL((k_grad_lap2_probes<D, HS, HT>), dim3(B), dim3(256), lds, c->stream, m, (const double*)c->d_theta, (const double*)c->d_spk,
+                               (const double*)c->d_tab, x, sidx, B, mode, nprobe, weight, v, grad, lap, (double*)c->ws, dl);
+            return 1;
+        }
+        if (D == 2 && HS == 16 && HT == 16) return cg_big_grad_lap_probes(c, m, x, sidx, B, mode, nprobe, v, weight, grad, lap);
+        return 0;
     });
 }
 

@@ -11,6 +11,8 @@
 
 int cg_derivs_b_grad_lap(cg_ctx* c, const CgDev& m, const double* x, const int* sidx, int B, int mode, const double* v,
                          double* grad, double* lap);
+int cg_derivs_b_grad_lap_probes(cg_ctx* c, const CgDev& m, const double* x, const int* sidx, int B, int mode, int nprobe, const double* v,
+                                double weight, double* grad, double* lap);
 int cg_derivs_b_param_vjp(cg_ctx* c, const CgDev& m, const double* x, const int* sidx, int B, double* score);
 int cg_derivs_b_scores(cg_ctx* c, const CgDev& m, const double* x, const int* sidx, int B, double* score);
 
@@ -229,7 +231,73 @@ static int small_grad_lap_scores(cg_ctx* c, const CgDev& m, const double* x, con
 int cg_big_grad_lap_scores(cg_ctx* c, const CgDev& m, const double* x, const int* sidx, int B, int mode, const double* v, double* grad, double* lap,
                            double* score);      // cg_k_big.hip
 
+// grad / Laplacian of B walkers with one probe each, device pointers: the general-depth kernel or the fast path's units.  CG_OK or an error.
+static int launch_grad_lap(cg_ctx* c, const char* fn, const double* x, const int* sidx, int B, int mode, const double* v, double* grad, double* lap) {
+    int rc;
+    if (!c->fast) return cg_gen_run_grad_lap(c, std::min(B, c->cu_count * 2 * CG_DERIV_WAVES), x, sidx, B, mode, v, grad, lap);
+    const CgDev m = make_dev(c);
+    if ((rc = cg_derivs_a_grad_lap(c, m, x, sidx, B, mode, v, grad, lap)) < 0) return rc;
+    if (rc == 0 && (rc = cg_derivs_b_grad_lap(c, m, x, sidx, B, mode, v, grad, lap)) < 0) return rc;
+    if (rc != 1) CG_FAIL(c, CG_ERR_UNSUPPORTED, "%s: configuration not instantiated", fn);
+    return CG_OK;
+}
+
+// cg_grad_laplacian_probes where no kernel has the probe loop: lap (B, 2) <- pf + weight sum_k (laps[k] - pf), k ascending; pf is the
+// single-probe result of the zero probe (the probe terms are quadratic in v: it is the probe-free part), laps (nprobe, B, 2) those of the probes
+__global__ void k_probe_combine(const double* __restrict__ pf, const double* __restrict__ laps, int count /* 2 B */, int nprobe, double weight,
+                                double* __restrict__ out) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= count) return;
+    const double p = pf[e];
+    double acc = laps[e] - p;
+    for (int k = 1; k < nprobe; ++k) acc += laps[(size_t)k * count + e] - p;
+    out[e] = p + weight * acc;
+}
+
 extern "C" {
+
+int cg_grad_laplacian_probes(cg_ctx* c, const double* x, const int32_t* sidx, int B, int mode, int nprobe, const double* v, double weight,
+                             double* grad, double* lap) {
+    int rc = check_ready(c, "cg_grad_laplacian_probes", B); if (rc) return rc;
+    if (mode != CG_LAP_HUTCHINSON && mode != CG_LAP_HUTCHINSON_SPLIT) CG_FAIL(c, CG_ERR_ARG, "cg_grad_laplacian_probes: mode %d (a Hutchinson mode is needed)", mode);
+    if (nprobe < 1) CG_FAIL(c, CG_ERR_ARG, "cg_grad_laplacian_probes: nprobe %d", nprobe);
+    if (!v) CG_FAIL(c, CG_ERR_ARG, "cg_grad_laplacian_probes: v is NULL");
+    if (B == 0) return CG_OK;
+    if (!x || !sidx || !grad || !lap) CG_FAIL(c, CG_ERR_ARG, "cg_grad_laplacian_probes: NULL argument");
+    const int n = c->n, N = n * c->dim;
+    const size_t BN = (size_t)B * N;
+    if ((size_t)nprobe > (~(size_t)0) / sizeof(double) / BN)
+        CG_FAIL(c, CG_ERR_ARG, "cg_grad_laplacian_probes: nprobe B n dim = %d x %zu doubles overflows size_t", nprobe, BN);
+    if ((rc = arena_reset(c))) CG_FAIL(c, rc, "cg_grad_laplacian_probes: arena");
+    Arg ax{(void*)x, nullptr, sizeof(double) * BN, true, false};
+    Arg as{(void*)sidx, nullptr, sizeof(int32_t) * (size_t)B * n, true, false};
+    Arg av{(void*)v, nullptr, sizeof(double) * BN * nprobe, true, false};
+    Arg ag{grad, nullptr, sizeof(double) * BN * 2, false, true};
+    Arg al{lap, nullptr, sizeof(double) * (size_t)B * 2, false, true};
+    Arg* all[] = {&ax, &as, &av, &ag, &al};
+    for (Arg* a : all) if ((rc = stage(c, *a))) return rc;
+    const double* xd = (const double*)ax.dev; const int* sd = (const int*)as.dev; const double* vd = (const double*)av.dev;
+    double* gd = (double*)ag.dev; double* ld = (double*)al.dev;
+    rc = 0;
+    if (c->fast) {      // a kernel with the probe loop: one set-up, nprobe jet passes
+        const CgDev m = make_dev(c);
+        if ((rc = cg_derivs_a_grad_lap_probes(c, m, xd, sd, B, mode, nprobe, vd, weight, gd, ld)) < 0) return rc;
+        if (rc == 0 && (rc = cg_derivs_b_grad_lap_probes(c, m, xd, sd, B, mode, nprobe, vd, weight, gd, ld)) < 0) return rc;
+    }
+    if (rc != 1) {      // none: the single-probe kernel on the zero probe and on each probe, combined on the device
+        double* zero = (double*)arena_take(c, sizeof(double) * BN);
+        double* laps = (double*)arena_take(c, sizeof(double) * 2 * (size_t)B * ((size_t)nprobe + 1));
+        if (!zero || !laps) CG_FAIL(c, CG_ERR_HIP, "cg_grad_laplacian_probes: workspace allocation failed");
+        double* pf = laps + 2 * (size_t)B * nprobe;
+        CG_HIP(c, hipMemsetAsync(zero, 0, sizeof(double) * BN, c->stream));
+        for (int k = 0; k < nprobe; ++k)
+            if ((rc = launch_grad_lap(c, "cg_grad_laplacian_probes", xd, sd, B, mode, vd + (size_t)k * BN, gd, laps + 2 * (size_t)B * k))) return rc;
+        if ((rc = launch_grad_lap(c, "cg_grad_laplacian_probes", xd, sd, B, mode, zero, gd, pf))) return rc;
+        hipLaunchKernelGGL(k_probe_combine, dim3((2 * B + 255) / 256), dim3(256), 0, c->stream, (const double*)pf, (const double*)laps, 2 * B, nprobe, weight, ld);
+    }
+    for (Arg* a : all) if ((rc = unstage(c, *a))) return rc;
+    return finish(c);
+}
 
 int cg_grad_laplacian(cg_ctx* c, const double* x, const int32_t* sidx, int B, int mode, const double* v,
                       double* grad, double* lap) {
@@ -247,19 +315,8 @@ int cg_grad_laplacian(cg_ctx* c, const double* x, const int32_t* sidx, int B, in
     Arg al{lap, nullptr, sizeof(double) * (size_t)B * 2, false, true};
     Arg* all[] = {&ax, &as, &av, &ag, &al};
     for (Arg* a : all) if ((rc = stage(c, *a))) return rc;
-    if (!c->fast) {
-        const int grid = std::min(B, c->cu_count * 2 * CG_DERIV_WAVES);
-        if ((rc = cg_gen_run_grad_lap(c, grid, (const double*)ax.dev, (const int*)as.dev, B, mode, (const double*)av.dev, (double*)ag.dev,
-                                      (double*)al.dev))) return rc;
-        for (Arg* a : all) if ((rc = unstage(c, *a))) return rc;
-        return finish(c);
-    }
-    const CgDev m = make_dev(c);
-    if ((rc = cg_derivs_a_grad_lap(c, m, (const double*)ax.dev, (const int*)as.dev, B, mode, (const double*)av.dev, (double*)ag.dev,
-                                   (double*)al.dev)) < 0) return rc;
-    if (rc == 0 && (rc = cg_derivs_b_grad_lap(c, m, (const double*)ax.dev, (const int*)as.dev, B, mode, (const double*)av.dev,
-                                              (double*)ag.dev, (double*)al.dev)) < 0) return rc;
-    if (rc != 1) CG_FAIL(c, CG_ERR_UNSUPPORTED, "cg_grad_laplacian: configuration not instantiated");
+    if ((rc = launch_grad_lap(c, "cg_grad_laplacian", (const double*)ax.dev, (const int*)as.dev, B, mode, (const double*)av.dev, (double*)ag.dev,
+                              (double*)al.dev))) return rc;
     for (Arg* a : all) if ((rc = unstage(c, *a))) return rc;
     return finish(c);
 }

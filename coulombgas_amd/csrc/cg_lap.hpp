@@ -36,6 +36,19 @@
 #define CG_UNR_G 4
 #endif
 
+// Several probes in one call (cg_grad_laplacian_probes), the rule both kernels (here and cg_big.hpp) follow: per thread the four
+// partial sums of the jet passes (Re / Im of v^T hess(log phi) v, t2, t3) accumulate in ascending probe order into an accumulator of
+// their own that starts from probe 0's values; the accumulator is scaled once by `weight` and then added to the thread's probe-free
+// partials, which are block-summed as in the single-probe call.  One probe with weight 1 is the single-probe arithmetic bit for bit.
+static CG_DEVI void cg_probe_add(double (&acc)[4], const double (&r)[4], int k) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i] = k == 0 ? r[i] : acc[i] + r[i];
+}
+static CG_DEVI void cg_probe_fold(double (&tot)[4], const double (&acc)[4], double weight) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) tot[i] += weight * acc[i];
+}
+
 template <int D, int HS, int HT>
 struct CgLap {
     using F = CgFast<D, HS, HT>;
@@ -1075,12 +1088,16 @@ struct CgLap {
         CG_STAMP_END(31)
     }
 
-    template <bool AL>
+    // MP (cg_grad_laplacian_probes; modes 1 and 2): nprobe probes v + k vstride for this walker, one set-up.  The jet pass reads the
+    // P block only (x, J^-1, g, and T^a / K^ab in mode 1) and re-forms every jet from x, so it is entered again as the exact mode's
+    // loop enters it; the partial sums of the passes are combined by cg_probe_add / cg_probe_fold.
+    template <bool AL, bool MP = false>
     static CG_DEVI void grad_laplacian(const CgBlk& b, const double* __restrict__ th, const double* __restrict__ xg,
                                        const double* __restrict__ spk, const int* __restrict__ sidx, int n, double L,
                                        int mode, const double* __restrict__ v, double* __restrict__ grad /*N x 2*/,
                                        double* __restrict__ lap /*2*/, double* lds, double* ws, const Lay& l,
-                                       double* stash = nullptr, const Stash* st = nullptr) {
+                                       double* stash = nullptr, const Stash* st = nullptr,
+                                       int nprobe = 1, size_t vstride = 0, double weight = 1.0) {
         const int N = n * D;
         const Mem<AL> mem(lds, ws, l);
         const bool exact_phi = mode != 1;
@@ -1115,6 +1132,15 @@ struct CgLap {
                 tot[2] += r[2]; tot[3] += r[3];
                 b.sync();
             }
+        } else if (MP) {
+            double acc[4];
+            for (int k = 0; k < nprobe; ++k) {
+                double r[4];
+                jet_part<AL>(b, th, n, L, mem, l, v + (size_t)k * vstride, 0, mode == 1, r);
+                cg_probe_add(acc, r, k);
+                b.sync();                            // the next pass overwrites the jet arena
+            }
+            cg_probe_fold(tot, acc, weight);
         } else {
             double r[4];
             jet_part<AL>(b, th, n, L, mem, l, v, 0, mode == 1, r);

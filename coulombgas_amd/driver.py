@@ -174,7 +174,7 @@ def format_row(i, data, rs, batch_total, acc_steps, accept_rate):
 def train(flow, params_flow, sp_indices, n, dim, L, rs, beta, batch, epochs, sampler, log_prob, params_van=None,
           optimizer=None, sr=None, kappa=10, Gmax=15, mc_therm=10, mc_steps=50, mc_stddev=0.1, acc_steps=1,
           hutchinson=True, seed=42, log=None, log_prob_vjp=None, classical_score_fn=None, comm=None, device_resident=True,
-          ckpt_path=None, ckpt_every=100, epoch_finished=0, structure=None, momentum=None):
+          ckpt_path=None, ckpt_every=100, epoch_finished=0, structure=None, momentum=None, hutchinson_probes=1):
     """main.py:216-384 on one rank.  sr = (damping, max_norm) selects hybrid_fisher_sr (main.py:179-184), otherwise
     `optimizer` (default adam(1e-3)).  Returns (params_van, params_flow, rows) with rows the data.txt lines.
     ckpt_path / ckpt_every / epoch_finished: the checkpoints of main.py:374-381 ({"keys", "x", "params_van", "params_flow",
@@ -183,7 +183,8 @@ def train(flow, params_flow, sp_indices, n, dim, L, rs, beta, batch, epochs, sam
     structure: an accumulator from make_structure_observable; every sampling call of the epoch loop (not the thermalisation rounds)
     adds its walkers to it, on the device.  None: nothing is called or allocated for it.
     momentum: an accumulator from make_momentum_observable, fed the walkers and state indices of the same sampling calls (shifts_per_particle
-    x n further log Psi evaluations per walker and call, with the flow parameters the call sampled with).  None: likewise nothing."""
+    x n further log Psi evaluations per walker and call, with the flow parameters the call sampled with).  None: likewise nothing.
+    hutchinson_probes: probes per walker of the Hutchinson Laplacian (make_logpsi_grad_laplacian(probes=...)); 1: the reference's one."""
     cm = comm or get_comm()
     if log_prob_vjp is None and hasattr(log_prob, "vjp"):          # make_autoregressive_sampler's log_prob carries its own
         log_prob_vjp = log_prob.vjp                                 # reverse pass: the density matrix is trained as well
@@ -245,7 +246,8 @@ def train(flow, params_flow, sp_indices, n, dim, L, rs, beta, batch, epochs, sam
     if thermalise:
         for _ in range(mc_therm):                                                      # :241-246
             key, _, x, _ = sample_stateindices_and_x(key, sampler, params_van, logp, x, params_flow, mc_steps, mc_stddev, L, comm=cm)
-    logpsi, lgl = make_logpsi_grad_laplacian(logpsi_novmap, hutchinson=hutchinson, logphi=logphi, logjacdet=logjacdet)   # :254-256
+    logpsi, lgl = make_logpsi_grad_laplacian(logpsi_novmap, hutchinson=hutchinson, logphi=logphi, logjacdet=logjacdet,    # :254-256
+                                             probes=hutchinson_probes)
     observable_and_lossfn = make_loss(log_prob, logpsi, lgl, kappa, G, L, rs, Vconst, beta, comm=cm)               # :258-259
     update = make_update(observable_and_lossfn, optimizer, acc_steps, fishers_fn, log_prob_vjp, comm=cm)
     rows = []

@@ -371,6 +371,30 @@ class Engine:
         lap = (l[:, 0] + 1j * l[:, 1]).reshape(lead)
         return grad, lap
 
+    def _probe_weight(self, K, weight):
+        return 1.0 / max(K, 1) if weight is None else float(weight)
+
+    def grad_laplacian_probes(self, x, state_idx, mode, v, weight=None):
+        """cg_grad_laplacian_probes: K probes v (K,) + x.shape per walker behind one set-up; lap = probe-free part + weight * sum_k
+        (probe terms of v[k]).  weight None: 1 / K, the Hutchinson mean."""
+        xb, lead = self._xb(x)
+        B = xb.shape[0]
+        s = self._sb(state_idx, B)
+        K = 1
+        if v is not None:
+            v = _f64(v)
+            K = v.shape[0] if v.ndim else 0
+            if v.shape != (K,) + tuple(np.shape(x)):
+                raise ValueError("v must have shape (K,) + x.shape = (K,) + %s, got %s" % (tuple(np.shape(x)), v.shape))
+            v = v.reshape(K, B, self.n, self.dim)
+        g = np.empty((B, self.n, self.dim, 2))
+        l = np.empty((B, 2))
+        check(lib().cg_grad_laplacian_probes(self._ctx, _p(xb), _p(s), B, int(mode), int(K), _p(v), self._probe_weight(K, weight), _p(g), _p(l)),
+              self._ctx)
+        grad = (g[..., 0] + 1j * g[..., 1]).reshape(lead + (self.n, self.dim))
+        lap = (l[:, 0] + 1j * l[:, 1]).reshape(lead)
+        return grad, lap
+
     # Per-sample scores resident on the device (cg_scores_*): one score computation (two reverse sweeps) serves the two
     # theta-VJPs of jax.jacrev(quantum_lossfn) (main.py:278) and the Fisher matrix of the SR optimizer, instead of one
     # sweep (and one set-up) each.  Valid while (x, state_idx, theta) are unchanged.
@@ -551,6 +575,22 @@ class Engine:
         else:
             self._dev_call(lib().cg_grad_laplacian, x_d.ptr, sidx_d.ptr, int(B), int(mode), v_d.ptr if v_d is not None else None, g.ptr, l.ptr)
         g.version += 1; l.version += 1
+        return g, l
+
+    def grad_laplacian_probes_d(self, x_d, sidx_d, mode, v_d, weight=None, with_scores=False):
+        """cg_grad_laplacian_probes on device-resident walkers; v_d (K,) + x_d.shape.  with_scores: scores_compute_d on the same walkers
+        follows (the fused kernel takes one probe only), so that the resident scores are where an optimisation step looks for them"""
+        B = x_d.shape[0]
+        K = int(v_d.shape[0]) if v_d is not None else 1
+        if v_d is not None and tuple(v_d.shape) != (K,) + tuple(x_d.shape):
+            raise ValueError("v must have shape (K,) + x.shape = (K,) + %s, got %s" % (tuple(x_d.shape), tuple(v_d.shape)))
+        g = self.scratch("grad", (B, self.n, self.dim), complex_pairs=True)
+        l = self.scratch("lap", (B,), complex_pairs=True)
+        self._dev_call(lib().cg_grad_laplacian_probes, x_d.ptr, sidx_d.ptr, int(B), int(mode), K, v_d.ptr if v_d is not None else None,
+                       self._probe_weight(K, weight), g.ptr, l.ptr)
+        g.version += 1; l.version += 1
+        if with_scores:
+            self.scores_compute_d(x_d, sidx_d)
         return g, l
 
     def ewald_d(self, x_d):

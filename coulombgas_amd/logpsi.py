@@ -83,11 +83,21 @@ def _is_device(a):
     return not isinstance(a, np.ndarray) and hasattr(a, "ptr")
 
 
-def make_logpsi_grad_laplacian(logpsi, forloop=True, hutchinson=False, logphi=None, logjacdet=None):
+def make_logpsi_grad_laplacian(logpsi, forloop=True, hutchinson=False, logphi=None, logjacdet=None, probes=1):
     """src/logpsi.py:55-172.  `forloop` selects between two algebraically identical reference
     variants (:86-100) and has no effect here.  With DeviceArray arguments the results are DeviceArrays too and the
-    probe is drawn on the device (cg_randn) unless `key` is an explicit probe array."""
+    probe is drawn on the device (cg_randn) unless `key` is an explicit probe array.
+
+    probes = K > 1 (not in the reference; hutchinson=True only): the Laplacian is the mean over K probes in one call
+    (cg_grad_laplacian_probes: one set-up per walker, K jet passes).  `key` is then an explicit array of shape (K,) + x.shape or a
+    seed: one cg_randn of K B n dim values on the device, one standard_normal((K,) + x.shape) on the host.  probes = 1 is the
+    single-probe path, call for call."""
     wf = logpsi.wf
+    probes = int(probes)
+    if probes < 1:
+        raise ValueError("probes must be >= 1, got %d" % probes)
+    if probes > 1 and not hutchinson:
+        raise ValueError("probes > 1 needs hutchinson=True (the exact mode takes no probe)")
 
     def logpsi_vmapped(x, params, state_idx):
         eng = wf.engine(x, params)
@@ -107,6 +117,19 @@ def make_logpsi_grad_laplacian(logpsi, forloop=True, hutchinson=False, logphi=No
         """with_scores (device arrays only; not in the reference's signature): also leave the per-sample scores d log Psi / d theta of
         the same walkers resident -- make_loss asks for it, because the jacrev of main.py:278 follows on the same x"""
         eng = wf.engine(x, params)
+        if probes > 1:
+            kshape = (probes,) + tuple(np.shape(x))
+            if isinstance(key, np.ndarray) and key.dtype.kind == "f" and key.shape != kshape:
+                raise ValueError("explicit probes must have shape (probes,) + x.shape = %s, got %s" % (kshape, key.shape))
+            if _is_device(x):
+                if isinstance(key, np.ndarray) and key.shape == kshape:
+                    v_d = eng.asdevice(key, "probes")
+                else:
+                    from .mcmc import _seed_of
+                    v_d = eng.randn_d("probes", kshape, _seed_of(key))
+                s_d = state_indices if _is_device(state_indices) else eng.asdevice(state_indices, "sidx", np.int32)
+                return eng.grad_laplacian_probes_d(x, s_d, mode, v_d, with_scores=with_scores)
+            return eng.grad_laplacian_probes(x, state_indices, mode, _draw_v(key, kshape))
         if _is_device(x):
             v_d = None
             if hutchinson:
@@ -122,6 +145,7 @@ def make_logpsi_grad_laplacian(logpsi, forloop=True, hutchinson=False, logphi=No
 
     logpsi_vmapped.wf = logpsi_grad_laplacian.wf = wf
     logpsi_grad_laplacian.mode = mode
+    logpsi_grad_laplacian.probes = probes
     logpsi_grad_laplacian.takes_with_scores = True
     return logpsi_vmapped, logpsi_grad_laplacian
 

@@ -182,6 +182,25 @@ int cg_momentum_sums(cg_ctx* ctx, const double* x, const int32_t* state_idx, int
 int cg_grad_laplacian(cg_ctx* ctx, const double* x, const int32_t* state_idx, int B, int mode,
                       const double* v, double* grad, double* lap);
 
+/* cg_grad_laplacian with nprobe >= 1 Hutchinson probes per walker in ONE call: the set-up (flow, Jacobian, the two inverses, T^a,
+ * reverse sweep, forward Laplacian) runs once per walker, only the second-order jet pass runs once per probe.
+ *   v (nprobe, B, n, dim): probe k is a batch-shaped array exactly as cg_grad_laplacian takes it
+ *   lap = (probe-free part) + weight * sum_k (probe terms of v_k)          mode CG_LAP_HUTCHINSON or CG_LAP_HUTCHINSON_SPLIT
+ * weight = 1 / nprobe: the Hutchinson mean over the probes.  weight = 1 with the n dim basis vectors as probes in the split mode: the exact
+ * Laplacian.  Per thread the partial sums of the probes accumulate in ascending k, are scaled once by weight and join the probe-free
+ * partials before the block sum (csrc/cg_lap.hpp: cg_probe_add / cg_probe_fold): nprobe = 1, weight = 1 is cg_grad_laplacian bit for bit;
+ * grad does not depend on the probes and is cg_grad_laplacian's bit for bit for every nprobe.
+ * Routes.  Kernels with the probe loop: depth-2 fast path, any (dim, spsize, tpsize), at the sizes whose every array lives in LDS (n <= 16
+ * for the (2, 16, 16) flow: k_grad_lap2_probes) and the (dim 2, 16, 16) flow at n > 16 (k_gradlap_big_probes; more than one probe runs
+ * in a placement plan of its own that keeps what the jet pass reads alive).  Every other configuration -- general depth, the other flows
+ * where they do not fit LDS, CG_BIG=0 / CG_BIG_LAP=0 -- runs cg_grad_laplacian's kernel nprobe + 1 times (each probe and the zero probe,
+ * which yields the probe-free part: the probe terms are quadratic in v) and combines the results on the device; there nprobe = 1 agrees
+ * with cg_grad_laplacian to rounding, not bit for bit.
+ * CG_ERR_ARG: mode CG_LAP_EXACT (or no mode), nprobe < 1, NULL v, nprobe B n dim doubles overflowing size_t; CG_ERR_STATE and
+ * CG_ERR_UNSUPPORTED as cg_grad_laplacian; nothing is launched then.  Both pointer modes.  B == 0 does nothing. */
+int cg_grad_laplacian_probes(cg_ctx* ctx, const double* x, const int32_t* state_idx, int B, int mode,
+                             int nprobe, const double* v, double weight, double* grad, double* lap);
+
 /* g_theta (P) = sum_b [ w_re[b] * d/dtheta Re log Psi_b + w_im[b] * d/dtheta Im log Psi_b ]:
  * the vector-Jacobian product jax.jacrev(quantum_lossfn) needs (src/VMC.py:69-76, main.py:278).
  * Workspace: per-sample scores of at most 1024 walkers at a time (16 P bytes each) plus the kernels' own slots; the
