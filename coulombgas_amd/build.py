@@ -91,6 +91,15 @@ def build_emul(force=False, sanitize=None):
     return out
 
 
+def build_pathmap(force=False):
+    """tests/host_emul/libcg_pathmap.so: the kernel path each configuration takes at each n, from the layout functions (host only)"""
+    src = os.path.join(ROOT, "tests", "host_emul", "cg_pathmap.cpp")
+    out = os.path.join(ROOT, "tests", "host_emul", "libcg_pathmap.so")
+    if force or _newer(out, hip_sources() + [src]):
+        _run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", out, src])
+    return out
+
+
 def build_oracle(force=False, sanitize=None):
     sanitize = sanitize_requested() if sanitize is None else sanitize
     src = os.path.join(ROOT, "oracle", "cg_oracle.c")
@@ -110,4 +119,4 @@ if __name__ == "__main__":
     if "--sanitize" in sys.argv:                            # the ASan + UBSan builds of the CPU-side libraries (tools/sanitize_cpu.sh)
         print(build_emul("--force" in sys.argv, True)); print(build_oracle("--force" in sys.argv, True)); sys.exit(0)
     f = "--force" in sys.argv
-    build_hip(f); build_emul(f); build_oracle(f)
+    build_hip(f); build_emul(f); build_pathmap(f); build_oracle(f)

@@ -346,7 +346,8 @@ int cg_create(cg_ctx** out, int device, int n, int dim, int depth, int spsize, i
         // maximum size of the LDS-resident path: J (n d)^2 + the per-particle factors must fit 160 KiB.  Beyond it (n > ~64
         // at d = 2) the same model runs on the general path (HBM workspace), which provides every entry point.
         const size_t NN = (size_t)n * dim;
-        if (sizeof(double) * (CG_TAB_DOUBLES + (size_t)c->lay.total + 2 * ((NN + 1) & ~(size_t)1) + 2) > 160 * 1024) {
+        // (the largest LDS image of the sampler kernels: k_mcmc / k_displaced_ratios keep x, the trial x and the occupied k vectors)
+        if (sizeof(double) * (CG_TAB_DOUBLES + (size_t)c->lay.total + 3 * ((NN + 1) & ~(size_t)1) + 2) > 160 * 1024) {
             c->fast = false;
             c->P = c->gm.nparam;
         }

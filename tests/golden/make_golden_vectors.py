@@ -8,7 +8,8 @@ reference): inputs + expected outputs in fp64.  Run once in the build container;
   golden_n49_d2.npz   (--n49) shipped parameters + walkers of data/n_49_..._rs_10.0 (Emax 36); Hutchinson variants only
   golden_n57_d2.npz, golden_n29_d2_rs1.npz   (--large) BASELINE configs 5 and 4: shipped parameters + walkers of
                       data/n_57_..._rs_10.0 (Emax 49) and data/n_29_..._rs_1.0; Hutchinson variants only
-each: x, state_idx, theta, sp_indices -> z, J, half_logdetJ, logphi, grad/lap (exact), lap (Hutchinson-split and full for the
+  golden_configs_exact.npz   (--configs-exact) the exact mode at the shapes of tests/config_shapes.py, see make_configs_exact
+each (but the last): x, state_idx, theta, sp_indices -> z, J, half_logdetJ, logphi, grad/lap (exact), lap (Hutchinson-split and full for the
 stored probe v), Ewald V, theta-VJP for stored weights, a 5-step Metropolis trajectory for stored noise.
 """
 import os, sys, time
@@ -111,7 +112,48 @@ def add_exact_to_large():
         print(name, "exact mode, walker 0: %.1fs" % (time.time() - t0), "lap", g["lap_exact1"], flush=True)
 
 
+def _config_exact_one(shape):
+    """exact-mode gradient and Laplacian (src/logpsi.py:63-106) of walker 0 of a shape of tests/config_shapes.py"""
+    from tests import config_shapes as cs
+    torch.set_num_threads(1)
+    cache = os.path.join(ROOT, "oracle", "_build", "exact_" + cs.key_of(shape) + ".npz")
+    if os.path.exists(cache):
+        return shape, dict(np.load(cache))
+    t0 = time.time()
+    dim, hs, ht, n = shape
+    s = cs.inputs(shape, 1, cs.DERIV_WS)
+    flow = R.FermiNet(2, hs, ht, s["L"])
+    params = R.flow_unravel(R.T(s["theta"]), 2, hs, ht, dim)
+    _, fn = R.make_logpsi_grad_laplacian(R.make_logpsi(flow, s["sp"], s["L"]))
+    g, l = fn(R.T(s["x"]), params, torch.as_tensor(s["sidx"].astype(np.int64)))
+    out = dict(theta=s["theta"], x=s["x"], sidx=s["sidx"], grad=g.numpy(), lap=l.numpy())
+    os.makedirs(os.path.dirname(cache), exist_ok=True)
+    np.savez(cache, **out)
+    print(shape, "%.1fs" % (time.time() - t0), "lap", out["lap"], flush=True)
+    return shape, out
+
+
+def make_configs_exact(workers):
+    """(--configs-exact [WORKERS]) golden_configs_exact.npz: the exact mode at every shape of tests/config_shapes.py that stands for a
+    mode-0 kernel path and is too large for the oracle at test time; per shape `<key>/theta`, `/x`, `/sidx` (inputs, one walker),
+    `/grad`, `/lap`.  A finished shape is kept in oracle/_build, so that an interrupted run resumes."""
+    import multiprocessing as mp
+    from tests import config_shapes as cs
+    shapes = [sh for sh in cs.shapes_of("L0") if sh[3] > cs.EXACT_LIVE_MAX_N]
+    shapes.sort(key=lambda sh: -sh[3])                      # the slow ones first
+    out = {}
+    with mp.get_context("spawn").Pool(workers) as pool:
+        for shape, res in pool.imap_unordered(_config_exact_one, shapes):
+            for k, v in res.items():
+                out[cs.key_of(shape) + "/" + k] = v
+    np.savez_compressed(os.path.join(HERE, cs.EXACT_GOLDEN), **{k: out[k] for k in sorted(out)})
+    print(cs.EXACT_GOLDEN, len(shapes), "shapes")
+
+
 if __name__ == "__main__":
+    if "--configs-exact" in sys.argv:
+        i = sys.argv.index("--configs-exact")
+        make_configs_exact(int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 4); sys.exit(0)
     if "--exact-large" in sys.argv:
         add_exact_to_large(); sys.exit(0)
     if "--n49" in sys.argv:

@@ -41,7 +41,11 @@ def _device(eng, x, sidx, shifts=None):
 
 
 # ---- 1 -------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n,dim,hs,ht", [(5, 2, 16, 16), (13, 2, 16, 16), (7, 3, 4, 4), (29, 2, 16, 16)])
+@pytest.mark.parametrize("n,dim,hs,ht", [(5, 2, 16, 16), (13, 2, 16, 16), (7, 3, 4, 4), (29, 2, 16, 16),
+                                         # k_displaced_ratios of the other configurations of the second translation unit, on the LU
+                                         # paths of tests/config_shapes.py: fused and two-phase wave-level, sequential in one wave
+                                         # and in four, the first-generation concurrent pair
+                                         (13, 2, 8, 8), (5, 2, 32, 32), (8, 3, 16, 16), (11, 3, 8, 8), (27, 2, 4, 4), (23, 3, 16, 16)])
 def test_ratios_against_the_oracle(n, dim, hs, ht):
     """|r / r_ref - 1| <= 2e-11 max(1, |Re log Psi|) with r_ref from the oracle's log Psi at the displaced and the base configuration
     (twice the bound test_gpu_parity.test_logpsi applies to one evaluation); both pointer modes give identical bits"""

@@ -9,6 +9,11 @@ Shapes: the smallest at which each code path can still go wrong --
   n32    (2, 16, 16) n = 32   planned kernel, last size with two rows per wave in the pair pass of the jet
   n33    (2, 16, 16) n = 33   planned kernel, first size with one row per wave
   n5d3   depth 3     n = 5    no probe-loop kernel: nprobe + 1 launches of the single-probe kernel, combined on the device
+  c8n13  (2, 8, 8)   n = 13   k_grad_lap2_probes of the other configurations of the second translation unit: one per hidden width and
+  c32n5  (2, 32, 32) n = 5      dimension (tests/config_shapes.py: the path map of these configurations)
+  c16n8  (3, 16, 16) n = 8
+  c8n7d3 (3, 8, 8)   n = 7
+  c8n17  (2, 8, 8)   n = 17   such a configuration beyond the all-LDS kernel: single-probe launches of k_grad_lap2<AL = false>, combined
 B = 3 walkers, K in {1, 2, 5}.  The single-probe results, and the oracle's, are computed once per (shape, mode) and shared."""
 import numpy as np
 import pytest
@@ -18,9 +23,11 @@ from tests.common import GOLDEN, orbitals, box_length, flow_theta, state_indices
 pytestmark = pytest.mark.gpu
 
 SHAPES = {"n5": (5, 2, 2, 16, 16), "n13": (13, 2, 2, 16, 16), "n7d3": (7, 3, 2, 4, 4), "n17": (17, 2, 2, 16, 16),
-          "n32": (32, 2, 2, 16, 16), "n33": (33, 2, 2, 16, 16), "n5d3": (5, 2, 3, 16, 16)}
-NATIVE = [("n5", 2), ("n13", 1), ("n13", 2), ("n7d3", 2), ("n17", 2), ("n32", 1), ("n32", 2), ("n33", 2)]
-EVERY = NATIVE + [("n5d3", 2)]
+          "n32": (32, 2, 2, 16, 16), "n33": (33, 2, 2, 16, 16), "n5d3": (5, 2, 3, 16, 16),
+          "c8n13": (13, 2, 2, 8, 8), "c32n5": (5, 2, 2, 32, 32), "c16n8": (8, 3, 2, 16, 16), "c8n7d3": (7, 3, 2, 8, 8), "c8n17": (17, 2, 2, 8, 8)}
+NATIVE = [("n5", 2), ("n13", 1), ("n13", 2), ("n7d3", 2), ("n17", 2), ("n32", 1), ("n32", 2), ("n33", 2),
+          ("c8n13", 1), ("c8n13", 2), ("c32n5", 2), ("c16n8", 1), ("c16n8", 2), ("c8n7d3", 2)]
+EVERY = NATIVE + [("n5d3", 2), ("c8n17", 1), ("c8n17", 2)]
 KS = (1, 2, 5)
 B = 3
 

@@ -161,3 +161,65 @@ def test_second_generation_scores_vs_golden(name):
     assert np.abs(vjp - g["vjp"]).max() < 1e-10 * np.abs(g["vjp"]).max()
     S1 = eng.quantum_score(x, s)
     assert np.abs(S2 - S1).max() < 1e-11 * np.abs(S1).max()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the derivative-family shapes of tests/test_gpu_configs.py up to n = 24, through the same device code on the host: when a GPU assertion
+# of that file fails, this tells whether the formulas or the parallel execution are at fault
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _config_shapes(families, max_n=24):
+    from tests import config_shapes as cs
+    return sorted(sh for sh, fams in cs.SHAPES.items() if sh[3] <= max_n and set(fams) & set(families))
+
+
+@pytest.mark.parametrize("shape", _config_shapes(("L1", "L2")), ids=str)
+def test_config_shapes_hutchinson_modes_vs_oracle(shape):
+    import torch
+    from oracle import cg_ref as R
+    from tests import config_shapes as cs
+    dim, hs, ht, n = shape
+    B = 1
+    s = cs.inputs(shape, B, cs.DERIV_WS)
+    x, sidx = s["x"], s["sidx"]
+    v = s["rng"].standard_normal(x.shape)
+    eng = EmulEngine(n, dim, 2, hs, ht, s["L"], s["sp"]); eng.set_params(s["theta"])
+    rflow = R.FermiNet(2, hs, ht, s["L"])
+    rparams = R.flow_unravel(R.T(s["theta"]), 2, hs, ht, dim)
+    r_logpsi = R.make_logpsi(rflow, s["sp"], s["L"])
+    r_logphi, r_logjacdet = R.make_logphi_logjacdet(rflow, s["sp"], s["L"])
+    sb = torch.as_tensor(sidx.astype(np.int64))
+    grads = {}
+    for mode in (1, 2):
+        if "L%d" % mode not in cs.SHAPES[shape]:
+            continue
+        kw = dict(hutchinson=True) if mode == 1 else dict(hutchinson=True, logphi=r_logphi, logjacdet=r_logjacdet)
+        _, rfn = R.make_logpsi_grad_laplacian(r_logpsi, **kw)
+        gr, lr = rfn(R.T(x), rparams, sb, R.T(v))
+        gr, lr = gr.numpy(), lr.numpy()
+        g, l = eng.grad_laplacian(x, sidx, mode, v)
+        assert np.abs(g - gr).max() < 1e-10 * max(1.0, np.abs(gr).max()), mode
+        assert np.abs(l - lr).max() < 1e-9 * max(1.0, np.abs(lr).max()), mode
+        grads[mode] = g
+    if len(grads) == 2:
+        assert np.abs(grads[1] - grads[2]).max() < 1e-10 * max(1.0, np.abs(grads[1]).max())
+
+
+@pytest.mark.parametrize("shape", sorted(set(_config_shapes(("Q",))) | {(3, 16, 16, 8), (3, 16, 16, 9)}), ids=str)
+def test_config_shapes_scores_vs_oracle(shape):
+    """the first-generation scores (cg_derivs.hpp) at every score shape, and the second generation (cg_score.hpp) where the GPU library
+    runs it for a configuration of the second translation unit: (3, 16, 16) at n = 8 and 9"""
+    import torch
+    from oracle import cg_ref as R
+    from tests import config_shapes as cs
+    dim, hs, ht, n = shape
+    B = 2
+    s = cs.inputs(shape, B, cs.DERIV_WS)
+    x, sidx = s["x"], s["sidx"]
+    eng = EmulEngine(n, dim, 2, hs, ht, s["L"], s["sp"]); eng.set_params(s["theta"])
+    r_logpsi = R.make_logpsi(R.FermiNet(2, hs, ht, s["L"]), s["sp"], s["L"])
+    lpt = lambda xb, th, sbb: r_logpsi(xb, R.flow_unravel(th, 2, hs, ht, dim), sbb)
+    qr = R.make_quantum_score(lpt)(R.T(x), R.T(s["theta"]), torch.as_tensor(sidx.astype(np.int64))).numpy()
+    assert np.abs(eng.quantum_score(x, sidx) - qr).max() < 1e-10 * max(1.0, np.abs(qr).max())
+    if cs.paths(*shape)["Q"] == "k_scores":
+        assert shape[:3] == (3, 16, 16) and n in (8, 9)
+        assert np.abs(eng.quantum_score2(x, sidx) - qr).max() < 1e-10 * max(1.0, np.abs(qr).max())
