@@ -157,9 +157,24 @@ struct CgFast {
     static __device__ __forceinline__ d4_t mfma(double a, double bb, d4_t c) {
         return __builtin_amdgcn_mfma_f64_16x16x4f64(a, bb, c, 0, 0, 0);
     }
-    static __device__ __forceinline__ void load_pair_cols(const double* __restrict__ th_in, WFrag& w) {
+    // The MFMA B-operand fragments are (re)loaded inside every evaluation, and LICM must not hoist those loads out of the chain loop (they
+    // would be spilled).  What is made opaque is a zero OFFSET, not the pointer: the pointer then keeps its global address space, the loads
+    // are global_load (vmcnt alone) and not FLAT ones, which count on lgkmcnt as well and hold up the phase's first LDS operand read.
+    // CG_FRAG_LOADS_LAUNDERED_POINTER (the translation units of the derivative kernels define it): the pointer itself is laundered, as it was
+    // before the sampler's chain loop was tuned -- those kernels load the fragments outside any chain loop, and their code stays as it was.
+    static __device__ __forceinline__ const double* opaque_th(const double* __restrict__ th_in) {
+#if defined(CG_FRAG_LOADS_LAUNDERED_POINTER)
         const double* th = th_in;
-        asm volatile("" : "+s"(th));      // opaque to LICM (see load_dense_p)
+        asm volatile("" : "+s"(th));
+        return th;
+#else
+        unsigned off = 0;
+        asm volatile("" : "+s"(off));
+        return th_in + off;
+#endif
+    }
+    static __device__ __forceinline__ void load_pair_cols(const double* __restrict__ th_in, WFrag& w) {
+        const double* th = opaque_th(th_in);
         const int col = threadIdx.x & 15;
         w.th = th_in;
         w.tw[0] = th[o_t0b + col];
@@ -169,8 +184,7 @@ struct CgFast {
     // PART 0: every layer's fragments; 1 / 2 / 3: those of layer 0 / the last layer / the final projection only (primal_dense_mfma<true>)
     template <int PART = 0>
     static __device__ __forceinline__ void load_dense_p(const double* __restrict__ th_in, DenseP& w) {
-        const double* th = th_in;
-        asm volatile("" : "+s"(th));      // opaque to LICM: keep these loads inside the evaluation, not hoisted + spilled
+        const double* th = opaque_th(th_in);      // keep these loads inside the evaluation, not hoisted + spilled
         const int l = threadIdx.x & 63, col = l & 15, kq = l >> 4;
         if constexpr (PART == 0 || PART == 1) {
 #pragma unroll
@@ -191,8 +205,7 @@ struct CgFast {
         if constexpr (PART == 0 || PART == 3) w.bf = col < D ? th[o_fb + col] : 0.0;
     }
     static __device__ __forceinline__ void load_dense_j(const double* __restrict__ th_in, DenseJ& w) {
-        const double* th = th_in;
-        asm volatile("" : "+s"(th));      // opaque to LICM: keep these loads inside the evaluation, not hoisted + spilled
+        const double* th = opaque_th(th_in);      // keep these loads inside the evaluation, not hoisted + spilled
         const int l = threadIdx.x & 63, col = l & 15, kq = l >> 4;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
@@ -203,8 +216,7 @@ struct CgFast {
         }
     }
     static __device__ __forceinline__ void load_dense_u(const double* __restrict__ th_in, DenseU& w) {
-        const double* th = th_in;
-        asm volatile("" : "+s"(th));      // opaque to LICM: keep these loads inside the evaluation, not hoisted + spilled
+        const double* th = opaque_th(th_in);      // keep these loads inside the evaluation, not hoisted + spilled
         const int l = threadIdx.x & 63, col = l & 15, kq = l >> 4;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) w.w0t[ks] = col < P ? th[o_W0 + col * HS + 4 * ks + kq] : 0.0;   // B[k = g][col = f] = W0[f][g]
@@ -495,14 +507,14 @@ struct CgFast {
     // accumulators per direction collapse into two,  n^2 G_k[h][b] = sg1_k[h] A_b[k][h] + Q_b[k][h]  with
     //     A_b = sum_l' (c1 W0s C_b - c1 W0c S_b + c2c W0d R_b)[k][l'],   Q_b = sum_l' (-c1 W0s C_b - c1 W0c S_b + c2c W0d R_b)[k][l'] sg1_l'[h]
     // -- the same products, 64 accumulator registers fewer, G equal up to the order of the sums.
+    // FOLD also means one wave per workgroup: wave = 0, nw = 1 at compile time, the tile loops fold (see jac_factors_mfma).
     template <bool FOLD = false>
     static __device__ __forceinline__ void g_pass_mfma(const CgBlk& b, const WFrag& wfr, int n, double L, double* lds, const CgFastLds& o) {
-        const double* th = wfr.th;
-        asm volatile("" : "+s"(th));      // opaque to LICM (see load_dense_p)
+        const double* th = opaque_th(wfr.th);
         const double *sh = lds + o.sh, *ch = lds + o.ch, *sg1 = lds + o.sg1;
         double* G = lds + o.G;
         const int l = b.tid & 63, col = l & 15, kq = l >> 4;
-        const int wave = b.tid >> 6, nw = b.nthr >> 6;
+        const int wave = FOLD ? 0 : b.tid >> 6, nw = FOLD ? 1 : b.nthr >> 6;
         const int tiles = (n + 15) >> 4;
         const double rn = 1.0 / (double)n;
         const double c1 = 2.0 * CG_PI / L, c2c = CG_PI / (2.0 * L);
@@ -588,6 +600,7 @@ struct CgFast {
     }
     // dense part of primal(): needs m0, m1 in LDS; fills s1 sg1 sg2 s2 z.  Executed by wave 0; others wait.
     // LAZY (sampler with the pair cache, where registers are scarce): each layer's weight fragments are loaded right before that layer
+    // (and the workgroup is one wave: wave = 0, nw = 1 at compile time, the tile loops fold -- see jac_factors_mfma)
     template <bool LAZY = false>
     static __device__ __forceinline__ void primal_dense_mfma(const CgBlk& b, const WFrag& wfr, const double* x, int n,
                                                              double* lds, const CgFastLds& o) {
@@ -595,7 +608,7 @@ struct CgFast {
         double *m0 = lds + o.m0, *s1 = lds + o.s1, *sg1 = lds + o.sg1, *m1 = lds + o.m1, *gbar = lds + o.gbar,
                *sg2 = lds + o.sg2, *s2 = lds + o.s2, *z = lds + o.z;
         const int l = b.tid & 63, col = l & 15, kq = l >> 4;
-        const int wave = b.tid >> 6, nw = b.nthr >> 6;
+        const int wave = LAZY ? 0 : b.tid >> 6, nw = LAZY ? 1 : b.nthr >> 6;
         const int tiles = (n + 15) >> 4;
         const double rn = 1.0 / (double)n;
         // layer 0: u1 = m0 W0 + b0
@@ -667,14 +680,16 @@ struct CgFast {
         b.sync();
     }
     // U, Bm (which = 0) or V (which = 1) of jacobian(): rows r = (i,a).  wfl: Wf (HS x D) staged in LDS.
-    template <int WHICH>
+    // ONE (here and in jac_bg_mfma / jac_up_mfma): the workgroup is one wave (single-wave sampler specialised on n), so wave = 0 and
+    // nw = 1 at compile time and the tile loops below fold into straight-line code instead of divergent loops over an opaque lane id
+    template <int WHICH, bool ONE = false>
     static __device__ __forceinline__ void jac_factors_mfma(const CgBlk& b, const WFrag& wfr, int n, double* lds,
                                                             const CgFastLds& o, const double* wfl) {
         DenseJ w; load_dense_j(wfr.th, w);
         const double* sg2 = lds + o.sg2;
         double *U = lds + o.U, *V = lds + o.V, *Bm = lds + o.Bm;
         const int l = b.tid & 63, col = l & 15, kq = l >> 4;
-        const int wave = b.tid >> 6, nw = b.nthr >> 6;
+        const int wave = ONE ? 0 : b.tid >> 6, nw = ONE ? 1 : b.nthr >> 6;
         const int N = n * D, tiles = (N + 15) >> 4;
         const double rn = 1.0 / (double)n;
         for (int t = wave; t < tiles; t += nw) {
@@ -706,11 +721,12 @@ struct CgFast {
         }
     }
     // J[r][c] = sum_g Bm[r][g] G[g][c]  (r = (i,a), c = (k,b)): the rank-16 term B_i G_k of every block at once
+    template <bool ONE = false>
     static __device__ __forceinline__ void jac_bg_mfma(const CgBlk& b, int n, double* lds, const CgFastLds& o, double* Jext = nullptr) {
         const double *Bm = lds + o.Bm, *G = lds + o.G;
         double* J = Jext ? Jext : lds + o.J;
         const int l = b.tid & 63, col = l & 15, kq = l >> 4;
-        const int wave = b.tid >> 6, nw = b.nthr >> 6;
+        const int wave = ONE ? 0 : b.tid >> 6, nw = ONE ? 1 : b.nthr >> 6;
         const int N = n * D, tiles = (N + 15) >> 4;
         for (int tt = wave; tt < tiles * tiles; tt += nw) {
             const int t = tt / tiles, u = tt - t * tiles;
@@ -732,12 +748,13 @@ struct CgFast {
         }
     }
     // Up = (1/n) (U diag sg1) W0^T
+    template <bool ONE = false>
     static __device__ __forceinline__ void jac_up_mfma(const CgBlk& b, const WFrag& wfr, int n, double* lds, const CgFastLds& o) {
         DenseU w; load_dense_u(wfr.th, w);
         const double *sg1 = lds + o.sg1, *U = lds + o.U;
         double* Up = lds + o.Up;
         const int l = b.tid & 63, col = l & 15, kq = l >> 4;
-        const int wave = b.tid >> 6, nw = b.nthr >> 6;
+        const int wave = ONE ? 0 : b.tid >> 6, nw = ONE ? 1 : b.nthr >> 6;
         const int N = n * D, tiles = (N + 15) >> 4;
         const double rn = 1.0 / (double)n;
         for (int t = wave; t < tiles; t += nw) {
@@ -868,20 +885,20 @@ struct CgFast {
         if (!w.wt_resident) stage_wt(b, th, lds, o);
         CG_STAMP(4)
 #if !defined(CG_EXP_NO_DENSE)       /* timing experiment (garbage numbers): the MFMA dense phases free -- the bound on pipelining them */
-        jac_factors_mfma<0>(b, w, n, lds, o, wfl);
+        jac_factors_mfma<0, (NS > 0)>(b, w, n, lds, o, wfl);
 #endif
         CG_STAMP(5)
         g_pass_mfma<(NS > 0)>(b, w, n, L, lds, o);
         b.sync();
         CG_STAMP(6)
 #if !defined(CG_EXP_NO_DENSE)
-        jac_up_mfma(b, w, n, lds, o);
+        jac_up_mfma<(NS > 0)>(b, w, n, lds, o);
         b.sync();
         CG_STAMP(7)
-        jac_bg_mfma(b, n, lds, o, w.Jext);
+        jac_bg_mfma<(NS > 0)>(b, n, lds, o, w.Jext);
         b.sync();
         CG_STAMP(8)
-        jac_factors_mfma<1>(b, w, n, lds, o, wfl);
+        jac_factors_mfma<1, (NS > 0)>(b, w, n, lds, o, wfl);
 #endif
         b.sync();
         CG_STAMP(9)

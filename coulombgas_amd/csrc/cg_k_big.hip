@@ -7,6 +7,7 @@ __device__ unsigned long long cg_inv_ph[8];
 #define CG_INV_T_DECL unsigned long long tprev_ = 0;
 #define CG_INV_T(i) { if (b.tid == 0) { const unsigned long long t_ = __builtin_readcyclecounter(); if (i > 0) atomicAdd(&cg_inv_ph[i], t_ - tprev_); tprev_ = t_; } }
 #endif
+#define CG_FRAG_LOADS_LAUNDERED_POINTER      /* cg_flow_fast.hpp: opaque_th */
 #include "cg_host.hpp"
 #include "cg_big.hpp"
 #if defined(CG_INV_TRACE)

@@ -1,5 +1,6 @@
 // cg_k_derivs_a.hip -- derivative kernels of the (2, 16, 16) flow (every shipped run), the score reductions, the quantum Fisher
 // matrix and the entry points of the family.  The other instantiations are compiled in cg_k_derivs_b.hip.
+#define CG_FRAG_LOADS_LAUNDERED_POINTER      /* cg_flow_fast.hpp: opaque_th */
 #include "cg_host.hpp"
 #include "cg_derivs.hpp"
 #include "cg_lap.hpp"

@@ -1,4 +1,5 @@
 // cg_k_derivs_b.hip -- derivative kernels of the remaining (dim, spsize, tpsize) instantiations.
+#define CG_FRAG_LOADS_LAUNDERED_POINTER      /* cg_flow_fast.hpp: opaque_th */
 #include "cg_host.hpp"
 #include "cg_derivs.hpp"
 #include "cg_lap.hpp"

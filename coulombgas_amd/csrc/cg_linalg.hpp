@@ -803,6 +803,17 @@ __device__ __forceinline__ double cg_dpp_f64(double v) {
     return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
 }
 
+// Helpers of the wave-level LUs below.
+// Ballot of a comparison over the rows that are still live: the builtin on the comparison ITSELF is the compare's own mask, and the
+// finished rows are cleared with one s_andn2 from the wave-uniform copy of `done` (bit = lane).  __ballot(!done && cmp) compiles to
+// v_cndmask 0/1 + v_cmp_ne + a wait state instead, and short-circuits into a divergent branch where cmp holds a cross-lane read.
+__device__ __forceinline__ unsigned long long cg_ballot_live(bool cmp, unsigned long long donemask) {
+    return __builtin_amdgcn_ballot_w64(cmp) & ~donemask;
+}
+// The running determinant products are formed where they are written: unpinned, the compiler sinks the whole chain of products behind
+// the last column step (nothing left there to hide it) and keeps every pivot alive until then -- in SGPRs it has to spill to VGPR lanes.
+__device__ __forceinline__ void cg_pin(double& v) { asm volatile("" : "+v"(v)); }
+
 // log|det A|, A: N x N real in LDS (row-major, lda), N <= NMAX <= 32 (NMAX even).  scr: 32 doubles of LDS.
 template <int NMAX>
 __device__ __forceinline__ double cg_wave_lu2_logabsdet(const double* A, int N, int lda, double* scr) {
@@ -825,14 +836,14 @@ __device__ __forceinline__ double cg_wave_lu2_logabsdet(const double* A, int N, 
             // leaves the short path, which takes ~30 dependent instructions out of every step.
             int p = (int)__builtin_ctzll(~donemask);
             double piv = cg_readlane_f64(ak, p);
-            if (__ballot(!done && fabs(ak) * 0.25 > fabs(piv))) {
+            if (cg_ballot_live(fabs(ak) * 0.25 > fabs(piv), donemask)) {
                 const unsigned key = done ? 0u : (unsigned)(__double_as_longlong(fabs(ak)) >> 32) + 1u;
                 const unsigned mx = cg_wave_max_u32(key);
-                const unsigned long long mask = __ballot(key == mx && !done);
+                const unsigned long long mask = cg_ballot_live(key == mx, donemask);
                 p = mask ? (int)__builtin_ctzll(mask) : p;
                 piv = cg_readlane_f64(ak, p);
             }
-            prod.mul(piv);
+            prod.mul(piv); cg_pin(prod.m);
             const double rinv = cg_fast_rcp1(piv);
             const bool isp = r == (p >> 1);
             const double l = (done || isp) ? 0.0 : ak * rinv;
@@ -884,10 +895,10 @@ __device__ __forceinline__ void cg_wave_lu2_logdet_complex(const double* A, int 
             const double m2 = akr * akr + aki * aki;
             // threshold pivoting (see the real version): first unfinished row unless a candidate is > 4x larger in modulus
             int p = (int)__builtin_ctzll(~donemask);
-            if (__ballot(!done && m2 * 0.0625 > cg_readlane_f64(m2, p))) {
+            if (cg_ballot_live(m2 * 0.0625 > cg_readlane_f64(m2, p), donemask)) {
                 const unsigned key = done ? 0u : (unsigned)(__double_as_longlong(m2) >> 32) + 1u;
                 const unsigned mx = cg_wave_max_u32(key);
-                const unsigned long long mask = __ballot(key == mx && !done);
+                const unsigned long long mask = cg_ballot_live(key == mx, donemask);
                 p = mask ? (int)__builtin_ctzll(mask) : p;
             }
             const bool isp = r == (p >> 2);
@@ -903,6 +914,7 @@ __device__ __forceinline__ void cg_wave_lu2_logdet_complex(const double* A, int 
                 int ex; const double mxv = fmax(fabs(pm.re), fabs(pm.im)); (void)frexp(mxv, &ex);
                 pm.re = ldexp(pm.re, -ex); pm.im = ldexp(pm.im, -ex); pe += ex;
             }
+            cg_pin(pm.re); cg_pin(pm.im);
             const double rd = cg_fast_rcp1(piv.re * piv.re + piv.im * piv.im);
             const CgCplx rinv = {piv.re * rd, -piv.im * rd};
             CgCplx l = cmul({akr, aki}, rinv);
@@ -978,20 +990,20 @@ __device__ __forceinline__ void cg_wave_lu2_both(const double* A, int N, int lda
         }
         const double m2 = akr * akr + aki * aki;
         int pc = (int)__builtin_ctzll(~cmask);
-        const unsigned long long tr = rs ? __ballot(!rdone && fabs(ak) * 0.25 > fabs(piv)) : 0ull;
-        const unsigned long long tc = cs ? __ballot(!cdone && m2 * 0.0625 > cg_readlane_f64(m2, pc)) : 0ull;
+        const unsigned long long tr = rs ? cg_ballot_live(fabs(ak) * 0.25 > fabs(piv), rmask) : 0ull;
+        const unsigned long long tc = cs ? cg_ballot_live(m2 * 0.0625 > cg_readlane_f64(m2, pc), cmask) : 0ull;
         if (tr | tc) {                                   // a candidate more than 4x larger than the first unfinished row: full search
             if (tr) {
                 const unsigned key = rdone ? 0u : (unsigned)(__double_as_longlong(fabs(ak)) >> 32) + 1u;
                 const unsigned mx = cg_wave_max_u32(key);
-                const unsigned long long mask = __ballot(key == mx && !rdone);
+                const unsigned long long mask = cg_ballot_live(key == mx, rmask);
                 p = mask ? (int)__builtin_ctzll(mask) : p;
                 piv = cg_readlane_f64(ak, p);
             }
             if (tc) {
                 const unsigned key = cdone ? 0u : (unsigned)(__double_as_longlong(m2) >> 32) + 1u;
                 const unsigned mx = cg_wave_max_u32(key);
-                const unsigned long long mask = __ballot(key == mx && !cdone);
+                const unsigned long long mask = cg_ballot_live(key == mx, cmask);
                 pc = mask ? (int)__builtin_ctzll(mask) : pc;
             }
         }
@@ -999,7 +1011,7 @@ __device__ __forceinline__ void cg_wave_lu2_both(const double* A, int N, int lda
         const bool risp = rr == (p >> 1);
         double l = 0.0;
         if (rs) {
-            prod.mul(piv);
+            prod.mul(piv); cg_pin(prod.m);
             const double rinv = cg_fast_rcp1(piv);
             l = (rdone || risp) ? 0.0 : ak * rinv;
         }
@@ -1016,6 +1028,7 @@ __device__ __forceinline__ void cg_wave_lu2_both(const double* A, int N, int lda
                 int ex; const double mxv = fmax(fabs(pm.re), fabs(pm.im)); (void)frexp(mxv, &ex);
                 pm.re = ldexp(pm.re, -ex); pm.im = ldexp(pm.im, -ex); pe += ex;
             }
+            cg_pin(pm.re); cg_pin(pm.im);
             const double rd = cg_fast_rcp1(cpiv.re * cpiv.re + cpiv.im * cpiv.im);
             const CgCplx rinv = {cpiv.re * rd, -cpiv.im * rd};
             lc = cmul({akr, aki}, rinv);
